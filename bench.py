@@ -12,8 +12,19 @@ the per-bag predictions Y[T, C] to every rank (weak scaling: every rank owns --b
 Prints ONE JSON line (rank 0). `roofline` prices the dominant kernel (the gate kernel) with the
 ALGORITHMIC FLOPs of the literal reference computation against the bf16 dense
 MFMA peak; its time comes from HIP events around that kernel on the launch stream.
-`cpu_baseline` times the reference op sequence (oracle/mcdo_ref.py, torch CPU, with its own
-dropout RNG) on a bounded sample of the same workload on this host.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, runs the W warm-up steps, times
+the K steps and prints the line. `--full` adds every measurement that takes GPU or CPU time of its
+own: the --busy-seconds of load before the timed steps with the `cold_start` pass ahead of it,
+the in-kernel clock probe (`roofline.clock_mhz`), the MFMA ceiling calibration
+(`mfma_calibration`, `roofline.frac_of_measured`), the shared-heads, fp32 and one-bag-per-call
+lines, and `cpu_baseline`, which times the reference op sequence (oracle/mcdo_ref.py, torch CPU,
+with its own dropout RNG) on a bounded sample of the same workload on this host. Without `--full`
+those keys are null.
+
+`--dump-outputs DIR` writes what the last timed step computed (Y, A, A_mean, A_var) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import ctypes
@@ -179,15 +190,31 @@ def main():
                     help="cfg5 only: precision of the instances / ResNet / head operands")
     ap.add_argument("--dist-backend", default="nccl", help=argparse.SUPPRESS)   # rehearsal: gloo
     ap.add_argument("--same-device", action="store_true", help=argparse.SUPPRESS)  # ranks on cuda:0
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the --busy-seconds of load "
+                         "and the cold_start pass, the clock probe, the MFMA ceiling calibration, the "
+                         "shared-heads / fp32 / single-bag lines, config 5's drift against its fp32 "
+                         "pipeline, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (Y, A, A_mean, A_var) as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of an output above "
+                         f"{DUMP_MAX_ELEMS} elements); cfg3 and cfg4 only")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--busy-seconds", type=float, default=12.0,
-                    help="keep stepping (untimed) after the warm-up until the GPU has been busy this long")
+    ap.add_argument("--busy-seconds", type=float, default=None,
+                    help="keep stepping (untimed) after the warm-up until the GPU has been busy this long "
+                         "(default: 12 with --full, else 0)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the fp32 reference-precision and single-bag lines")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the shared-heads, fp32 reference-precision and single-bag lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-calibration", action="store_true",
-                    help="skip the MFMA ceiling calibration (roofline.measured_peak_tflops)")
+                    help="with --full: skip the MFMA ceiling calibration (roofline.measured_peak_tflops)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload in ("cfg5", "single"):
+        ap.error("--dump-outputs is implemented for --workload cfg3 and cfg4")
+    if args.busy_seconds is None:
+        args.busy_seconds = 12.0 if args.full else 0.0
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_calibration = True
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -245,10 +272,11 @@ def main():
         ids = list(range(rank * args.bags, (rank + 1) * args.bags))
         total_bags = world * args.bags
 
-    # headline: W warm-up steps, then untimed steps until the GPU has been busy --busy-seconds
-    # (the driver's utilisation sampler polls every few seconds), then K timed steps
+    # headline: W warm-up steps, then (--full) untimed steps until the GPU has been busy
+    # --busy-seconds, then K timed steps
     r = measure_batch(sizes, ids, T, args.dtype, bool(args.shared), dev, world, args.steps,
-                      args.warmup, busy_s=args.busy_seconds, gather=True, seed_rank=rank)
+                      args.warmup, busy_s=args.busy_seconds, gather=True, seed_rank=rank,
+                      clock_probe=args.full, dump_dir=args.dump_outputs)
     el, gate_ms, fused, nreg, nbytes_packed = r["el"], r["gate_ms"], r["fused"], r["regions"], r["packed_bytes"]
     # the box's own MFMA ceiling, measured right after the headline's timed steps (chip under load)
     if not args.no_calibration:
@@ -334,12 +362,31 @@ def _head(dev, shared, L=512, D=128, C=2):
     return ops.HeadTensors(*[torch.from_numpy(arrays[k]).to(dev) for k in ops.HeadTensors._fields])
 
 
+DUMP_MAX_ELEMS = 3 * 2 ** 20    # per dumped output: 12 MiB of float32, 4 outputs < 64 MB
+
+
+def dump_outputs(outputs, dump_dir, rank=0, world=1):
+    """--dump-outputs: every tensor of `outputs` as <dump_dir>/<name>.npy (float32; rank r > 0 of
+    a multi-GPU run writes <name>_rank<r>.npy). An output above DUMP_MAX_ELEMS elements is sampled
+    at DUMP_MAX_ELEMS sorted positions drawn by numpy's default_rng(0) from its flattened size, the
+    same positions for the same arguments."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, t in outputs.items():
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arr = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(dump_dir, name + (f"_rank{rank}" if world > 1 and rank else "") + ".npy"), arr)
+
+
 def measure_batch(sizes, ids, T, dtype, shared, dev, world, steps, warmup, busy_s=0.0, gather=False,
-                  seed_rank=0, path="auto"):
+                  seed_rank=0, path="auto", clock_probe=True, dump_dir=None):
     """Time `steps` passes of the hot path over one batch of bags resident in HBM: the gate
     launch(es) through the C ABI, per-bag statistics, and (N > 1 GPUs, gather) the all_gather of
     Y. HIP events on the launch stream bracket the gate kernel (the fused launch when it runs).
-    Returns wall seconds (max over ranks), the events' mean ms, the launch path."""
+    Returns wall seconds (max over ranks), the events' mean ms, the launch path. With dump_dir the
+    outputs of the last timed step are written there (dump_outputs)."""
     from mcgmil import _lib, ops
     lib = _lib.load()
     L, D, C = 512, 128, 2
@@ -445,20 +492,24 @@ def measure_batch(sizes, ids, T, dtype, shared, dev, world, steps, warmup, busy_
     torch.cuda.synchronize()
     busy = time.perf_counter() - t_busy
     el, gate_ms = timed_pass()
+    if dump_dir:
+        dump_outputs({"Y": Y, "A": A, "A_mean": Am, "A_var": Av}, dump_dir, seed_rank, world)
     # the clock the gate launch runs at: the third of five back-to-back (untimed) steps right after
     # the timed ones, its workgroups stamping s_memtime / s_memrealtime at start and end
     # (MCGMIL_CLOCK_PROBE). Not the first step after a synchronize: the chip raises its clock in the
     # idle gap, and such a launch read ~7% above the steady state that GRBM_GUI_ACTIVE / 8 / wall
     # gives for the timed launches (profiles/r06/grbm_clock.json)
-    rec = ops.clock_record(dev)
-    for i in range(5):
-        if i == 2:
-            a.debug, a.flags = ctypes.c_void_p(rec.data_ptr()), a.flags | _lib.CLOCK_PROBE
-        step()
-        if i == 2:
-            a.debug, a.flags = None, a.flags & ~_lib.CLOCK_PROBE
-    torch.cuda.synchronize()
-    clock = ops.clock_mhz(rec)
+    clock = None
+    if clock_probe:
+        rec = ops.clock_record(dev)
+        for i in range(5):
+            if i == 2:
+                a.debug, a.flags = ctypes.c_void_p(rec.data_ptr()), a.flags | _lib.CLOCK_PROBE
+            step()
+            if i == 2:
+                a.debug, a.flags = None, a.flags & ~_lib.CLOCK_PROBE
+        torch.cuda.synchronize()
+        clock = ops.clock_mhz(rec)
     if world > 1 and clock is not None:
         t = torch.tensor([clock["median"]], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MIN)     # the slowest rank's clock

@@ -10,15 +10,15 @@ Two precisions (--features):
   fp32  the reference's precision end to end: fp32 instances, the build's fp32 MFMA convolutions
         (mcgmil_conv2d_f32, conv32_kernel: fp32 operands and accumulation; the 3-channel stem in its
         gather mode, features.py) and fused BN kernels, fp32 head operands;
-  bf16  bf16 instances, the build's HIP backbone under autocast, bf16 head operands. The run
-        also pushes its last image through the fp32 pipeline (same seed, untimed) and reports
-        the drift of prob_mean / A_mean / Y against it.
+  bf16  bf16 instances, the build's HIP backbone under autocast, bf16 head operands. With
+        --full the run also pushes its last image through the fp32 pipeline (same seed, untimed)
+        and reports the drift of prob_mean / A_mean / Y against it.
 
 A step = one image through all of that, the image already resident in HBM. Each rank runs its
 own image per step (images are independent: weak scaling, no collective on the data path).
 `roofline` prices the dominant stage, the ResNet-18 convolutions (3.64 GFLOP per 224 x 224
 instance: 1.82 GMAC, torchvision's published count), against the bf16 dense MFMA peak.
-`cpu_baseline` times the same pipeline on the host (oracle/patcher_ref.py, the in-repo ResNet
+`cpu_baseline` (--full) times the same pipeline on the host (oracle/patcher_ref.py, the in-repo ResNet
 in fp32 and oracle/mcdo_ref.py with torch's dropout RNG) on a bounded sample, extrapolated to
 one image.
 """
@@ -148,7 +148,7 @@ def run(args, world, rank, dev, peak_tflops, calib=None):
     if rank != 0:
         return None
     drift = None
-    if bf16:      # the same image and seed through the fp32 pipeline (untimed)
+    if bf16 and args.full:      # the same image and seed through the fp32 pipeline (untimed)
         seed = 1000 * rank + args.warmup + args.steps - 1
         ob = step(args.warmup + args.steps - 1)
         model.compute_dtype = torch.float32

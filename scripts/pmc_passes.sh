@@ -1,5 +1,5 @@
 #!/bin/bash
-# rocprofv3 counter passes on the headline bench command (python3 bench.py: 512 config-3 bags per
+# rocprofv3 counter passes on the headline bench command (python3 bench.py --full: 512 config-3 bags per
 # step), one pass per block group as MI355X_MICROARCH.md prescribes (<= 8 SQ, 4 TCC, 4 TCP, 2 TA,
 # 2 TD, 2 GRBM counters each; no tracing besides --kernel-trace). Each pass under its own hard time
 # limit; the script stops at the first pass that does not exit 0. A pass whose counters are not in
@@ -9,7 +9,7 @@ set -u
 OUT=${PMC_OUT:-gpurun_out/pmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD=${PMC_CMD:-"python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"}
+CMD=${PMC_CMD:-"python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"}
 if [ ! -s "$OUT/avail.txt" ]; then
     timeout -s KILL 120 rocprofv3 --list-avail > "$OUT/avail.txt" 2>&1 || true
 fi

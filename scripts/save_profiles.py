@@ -48,7 +48,7 @@ def main(tag):
         traffic["hbm_bytes_per_launch"] = int(
             (2 * traffic.get("FETCH_SIZE_KiB", 0) + traffic.get("WRITE_SIZE_KiB", 0)) * 1024)
         traffic["correction"] = "2 x FETCH_SIZE (gfx950 half-counting of wide reads) + WRITE_SIZE"
-        traffic["command"] = ("rocprofv3 --pmc <CTR> --kernel-trace -- python bench.py --steps 3 "
+        traffic["command"] = ("rocprofv3 --pmc <CTR> --kernel-trace -- python bench.py --full --steps 3 "
                               "--warmup 1 --no-cpu-baseline (bench defaults: 16 bags x N=2048, "
                               "T=100, bf16, separate attention)")
         traffic["config"] = {"bags": 16, "N": 2048, "T": 100, "dtype": "bf16", "shared": 0}
