@@ -7,6 +7,9 @@ HIP kernels behind the C ABI in include/mcgmil.h (libmcgmil.so, loaded with ctyp
   model.MultiHeadGatedAttentionMIL   the reference nn.Module API (ctor, state_dict, forward,
                                      mc_inference, mc_inference_serial) + mc_inference_features
   ops.mcdo_forward                   batched varlen entry (many bags x T samples, one launch)
+  ops.mcdo_backward                  its backward pass in HIP (include/mcgmil_grad.h; masks redrawn, not
+                                     stored); torch.ops.mcgmil.mcdo_forward is differentiable through it,
+                                     and model.enable_head_training() opts forward() into training
   library                            torch.ops.mcgmil.mcdo_forward(_stats): the same entry as
                                      torch.library custom ops (fake kernels for graph capture)
   infer.mc_predict_bags              caller-side uncertainty summary (reference infer.py)

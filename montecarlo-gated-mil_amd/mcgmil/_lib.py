@@ -49,6 +49,9 @@ EXPORTED = (
     "mcgmil_mfma_calib_flops_per_step", "mcgmil_mfma_calib",
 )
 
+# include/mcgmil_grad.h (the head's backward pass; purely additive to the ABI above)
+GRAD_EXPORTED = ("mcgmil_grad_args_size", "mcgmil_grad_workspace_size", "mcgmil_head_backward")
+
 _vp = ctypes.c_void_p
 
 
@@ -69,6 +72,21 @@ class Args(ctypes.Structure):
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("debug", _vp),
         ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
+
+
+class GradArgs(ctypes.Structure):
+    """Mirror of struct mcgmil_grad_args (include/mcgmil_grad.h)."""
+    _fields_ = [
+        ("fwd", Args), ("A", _vp), ("Y", _vp), ("dY", _vp), ("dA", _vp),
+        ("dWv", _vp), ("dbv", _vp), ("dWu", _vp), ("dbu", _vp), ("dwa", _vp), ("dba", _vp),
+        ("dwk", _vp), ("dH", _vp), ("ldh_grad", ctypes.c_int64),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+        ("chunk_pairs", ctypes.c_int64), ("reserved", ctypes.c_int64),
+    ]
+
+
+GRAD_GRANULE_ROWS = 512            # MCGMIL_GRAD_GRANULE_ROWS
+GRAD_DEFAULT_CHUNK_PAIRS = 32768   # MCGMIL_GRAD_DEFAULT_CHUNK_PAIRS
 
 
 class ImageArgs(ctypes.Structure):
@@ -193,6 +211,15 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
                           f"ctypes mirror is {ctypes.sizeof(Args)} bytes")
     if mcdo_only:
         return L
+    pg = ctypes.POINTER(GradArgs)
+    L.mcgmil_grad_args_size.restype = ctypes.c_size_t
+    L.mcgmil_grad_workspace_size.argtypes = [pg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_grad_workspace_size.restype = ctypes.c_int
+    L.mcgmil_head_backward.argtypes = [pg, _vp]
+    L.mcgmil_head_backward.restype = ctypes.c_int
+    if L.mcgmil_grad_args_size() != ctypes.sizeof(GradArgs):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_grad_args)={L.mcgmil_grad_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(GradArgs)} bytes")
     pi = ctypes.POINTER(ImageArgs)
     L.mcgmil_image_args_size.restype = ctypes.c_size_t
     L.mcgmil_tile_grid.argtypes = [pi, _vp, _vp, _vp, _vp]

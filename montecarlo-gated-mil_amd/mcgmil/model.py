@@ -12,9 +12,14 @@ What differs, by design:
     generator, so torch.manual_seed(...) still makes a run reproducible (infer.py:137-145);
   - mc_inference and mc_inference_serial give identical samples for the same seed (the
     reference's two methods consume its RNG in different orders);
-  - the head runs only on a HIP device and only without autograd: training (net_utils.py
-    train_gacc) is out of scope and raises instead of silently running elsewhere.
-Extra entry: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features).
+  - the head runs only on a HIP device. Training (net_utils.py train_gacc, main.py,
+    cross_validation.py) is opt-in: after enable_head_training(), forward() in train mode runs the
+    backbone under torch autograd and the head through the differentiable op
+    torch.ops.mcgmil.mcdo_forward, whose HIP backward (include/mcgmil_grad.h) draws the dropout
+    masks again instead of storing them. Without the opt-in, forward() in train mode raises
+    instead of silently running elsewhere.
+Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
+forward_features(H, T, seed) is its differentiable form.
 """
 import torch
 import torch.nn as nn
@@ -89,6 +94,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         # GEMM operand precision of the kernel: float32 (reference numerics) or bfloat16
         self.compute_dtype = torch.float32
         self._head_cache = None
+        self._head_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -217,14 +223,70 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                  "P_mean": out["P_mean"]}
         return Y, A, stats
 
+    # ------------------------------------------------------------------ training (opt-in)
+    def enable_head_training(self, flag=True):
+        """Let forward() in train mode build an autograd graph: backbone under torch autograd, head
+        through the differentiable HIP op (fp32). Off by default; returns self."""
+        self._head_training = bool(flag)
+        return self
+
+    def _live_head(self):
+        """The head parameters stacked for the kernel WITH their autograd history."""
+        lv, lu = self._gate_linears()
+        return (torch.stack([m.weight for m in lv]), torch.stack([m.bias for m in lv]),
+                torch.stack([m.weight for m in lu]), torch.stack([m.bias for m in lu]),
+                torch.cat([m.weight for m in self.attention_weights]),
+                torch.cat([m.bias for m in self.attention_weights]),
+                torch.cat([m.weight for m in self.classifiers]))
+
+    def forward_features(self, H, T=1, seed=None, *, p_feat=None, p_att=None, bag_id_base=0,
+                         t_base=0):
+        """mc_inference_features with a graph: H [n, L] or [bs, n, L] -> (Y [T, bs, C],
+        A [T, bs, C, n]), differentiable in H and the head parameters (fp32 only). The dropout
+        rates default to the active ones (_dropout_ps)."""
+        from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+        if H.dim() == 2:
+            H = H.unsqueeze(0)
+        device = self._check_device(H.device)
+        if self.compute_dtype != torch.float32:
+            raise NotImplementedError("the head's backward pass is built for compute_dtype=float32 only")
+        bs, n, L = H.shape
+        if seed is None:
+            seed = _draw_seed()
+        seed &= 2**64 - 1
+        if seed >= 2**63:                    # the op's schema takes the key as a signed int64
+            seed -= 2**64
+        pf, pa = self._dropout_ps()
+        pf = pf if p_feat is None else p_feat
+        pa = pa if p_att is None else p_att
+        params = [p.to(device=device, dtype=torch.float32).contiguous() for p in self._live_head()]
+        Hc = H.reshape(bs * n, L).to(torch.float32).contiguous()
+        Y, A = torch.ops.mcgmil.mcdo_forward(Hc, self._offsets(n, bs, device), *params, T, float(pf),
+                                             float(pa), seed, bag_id_base, t_base)
+        C = self.num_classes
+        return Y.permute(1, 0, 2), A.view(bs, T, C, n).permute(1, 0, 2, 3)
+
     # ------------------------------------------------------------------ reference API
-    def forward(self, x, targets=None):
+    def forward(self, x, targets=None, *, seed=None):
         """reference model.py:211-253. Returns (Y [bs, C], A_all [bs, C, n], aux_loss | None).
-        Dropout is applied by the layers that are in train mode (eval(): none)."""
+        Dropout is applied by the layers that are in train mode (eval(): none). In train mode
+        with gradients enabled it needs enable_head_training(); `seed` is then the Philox key of
+        the step's dropout masks (None: drawn from torch's default CPU generator)."""
         if torch.is_grad_enabled() and self.training and any(p.requires_grad
                                                             for p in self.parameters()):
-            raise NotImplementedError("training is out of scope for the MI355X MCDO build; "
-                                      "call forward() in eval mode or under torch.no_grad()")
+            if not self._head_training:
+                raise NotImplementedError("training is out of scope for the MI355X MCDO build; "
+                                          "call forward() in eval mode or under torch.no_grad() "
+                                          "(or opt in with enable_head_training())")
+            H = self.extract_features(x)
+            Y, A = self.forward_features(H, T=1, seed=seed)
+            Y, A = Y[0], A[0]
+            aux = None
+            if targets is not None:
+                is_positive = targets.item() == 1
+                aux = self.auxiliary_loss.scale * self.auxiliary_loss(A[:, 1, :], A[:, 0, :],
+                                                                      is_positive)
+            return Y, A, aux
         with torch.no_grad():
             H = self.extract_features(x)
             pf, pa = self._dropout_ps()

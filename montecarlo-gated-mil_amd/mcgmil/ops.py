@@ -256,6 +256,68 @@ def mcdo_forward(H: torch.Tensor, bag_offsets: torch.Tensor, head: HeadTensors, 
     return out
 
 
+GRAD_NAMES = ("dWv", "dbv", "dWu", "dbu", "dwa", "dba", "dwk")
+
+
+def mcdo_backward(H: torch.Tensor, bag_offsets: torch.Tensor, head: HeadTensors, T: int,
+                  A: torch.Tensor, Y: torch.Tensor, dY: torch.Tensor,
+                  dA: Optional[torch.Tensor] = None, *, p_feat: float, p_att: float, seed: int,
+                  bag_id_base: int = 0, t_base: int = 0, bag_ids: Optional[torch.Tensor] = None,
+                  need_dH: bool = True, outputs: Optional[Sequence[str]] = None,
+                  out: Optional[dict] = None, chunk_pairs: int = 0) -> dict:
+    """Gradients of mcdo_forward (mcgmil_head_backward): from the call's own arguments, its saved
+    A [T*C*total_rows] and Y [B, T, C], and the incoming dY [B, T, C] and optional dA (A's layout).
+    The dropout masks are drawn again from (seed, bag counter, t_base + t, row, column); none is
+    stored. fp32 H only. Returns a dict of fp32 tensors in parameter layout: dWv, dbv, dWu, dbu,
+    dwa, dba, dwk (or the subset named in `outputs`) and, with need_dH, dH [total_rows, L] summed
+    over the T samples. `out` supplies preallocated tensors by name (they are overwritten);
+    chunk_pairs caps the (sample, row) pairs in the workspace at once (0 = the library default) and
+    never changes a bit of the result."""
+    L = _lib.load()
+    _validate_inputs(H, bag_offsets)
+    if H.dtype != torch.float32:
+        raise ValueError(f"the backward pass takes fp32 features, got {H.dtype}")
+    dev = H.device
+    _check_head(head, dev)
+    if head.L != H.shape[1]:
+        raise ValueError(f"H has L={H.shape[1]}, the head expects L={head.L}")
+    g = _lib.GradArgs()
+    g.fwd = make_args(H, bag_offsets, head, T, head.C, head.G, head.D, p_feat, p_att, seed,
+                      bag_id_base, t_base, bag_ids=bag_ids)
+    B, R, C = g.fwd.num_bags, g.fwd.total_rows, head.C
+    for name, t, numel in (("A", A, T * C * R), ("Y", Y, B * T * C), ("dY", dY, B * T * C),
+                           ("dA", dA, T * C * R)):
+        if t is None and name == "dA":
+            continue
+        _require_cuda(name, t, torch.float32)
+        if t.numel() != numel or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of {numel} elements on {dev}")
+    g.A, g.Y, g.dY, g.dA = _p(A), _p(Y), _p(dY), _p(dA)
+    names = GRAD_NAMES if outputs is None else tuple(outputs)
+    if any(n not in GRAD_NAMES for n in names):
+        raise ValueError(f"outputs must be a subset of {GRAD_NAMES}")
+    res = {}
+    for n in names + (("dH",) if need_dH else ()):
+        like = H if n == "dH" else getattr(head, n[1:])
+        t = None if out is None else out.get(n)
+        if t is None:
+            t = torch.empty_like(like, memory_format=torch.contiguous_format)
+        else:
+            _require_cuda(n, t, torch.float32)
+            if t.shape != like.shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"out[{n!r}] must be a contiguous fp32 tensor of shape {tuple(like.shape)}")
+        res[n] = t
+        setattr(g, n, _p(t))
+    g.ldh_grad = H.shape[1]
+    g.chunk_pairs = int(chunk_pairs)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_grad_workspace_size(ctypes.byref(g), ctypes.byref(n)), "mcgmil_grad_workspace_size")
+    ws = torch.empty(max(n.value, 1), dtype=torch.uint8, device=dev)
+    g.workspace, g.workspace_bytes = _p(ws), n.value
+    _lib.check(L.mcgmil_head_backward(ctypes.byref(g), _stream(dev)), "mcgmil_head_backward")
+    return res
+
+
 def clock_record(device) -> torch.Tensor:
     """A zeroed MCGMIL_CLOCK_PROBE record (args.debug): int64 [MCGMIL_CLOCK_SLOTS, 4]."""
     return torch.zeros(_lib.CLOCK_SLOTS, 4, dtype=torch.int64, device=device)
