@@ -51,6 +51,9 @@ EXPORTED = (
 
 # include/mcgmil_grad.h (the head's backward pass; purely additive to the ABI above)
 GRAD_EXPORTED = ("mcgmil_grad_args_size", "mcgmil_grad_workspace_size", "mcgmil_head_backward")
+# include/mcgmil_conv_grad.h (the fp32 convolution's weight gradient; additive as well)
+CONV_GRAD_EXPORTED = ("mcgmil_conv_grad_args_size", "mcgmil_conv_wgrad_workspace_size_f32",
+                      "mcgmil_conv2d_wgrad_f32")
 
 _vp = ctypes.c_void_p
 
@@ -120,6 +123,18 @@ class ConvArgs(ctypes.Structure):
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
         ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
+
+
+class ConvGradArgs(ctypes.Structure):
+    """Mirror of struct mcgmil_conv_grad_args (include/mcgmil_conv_grad.h)."""
+    _fields_ = [
+        ("fwd", ConvArgs), ("dy", _vp), ("dw", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+        ("chunk_pixels", ctypes.c_int64), ("reserved", ctypes.c_int64),
+    ]
+
+
+WGRAD_GRANULE_PIXELS = 2048        # MCGMIL_WGRAD_GRANULE_PIXELS
 
 
 class StemArgs(ctypes.Structure):
@@ -258,6 +273,15 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     L.mcgmil_pack_conv_weights_f32.restype = ctypes.c_int
     L.mcgmil_conv2d_f32.argtypes = [pc, _vp]
     L.mcgmil_conv2d_f32.restype = ctypes.c_int
+    pcg = ctypes.POINTER(ConvGradArgs)
+    L.mcgmil_conv_grad_args_size.restype = ctypes.c_size_t
+    L.mcgmil_conv_wgrad_workspace_size_f32.argtypes = [pcg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_conv_wgrad_workspace_size_f32.restype = ctypes.c_int
+    L.mcgmil_conv2d_wgrad_f32.argtypes = [pcg, _vp]
+    L.mcgmil_conv2d_wgrad_f32.restype = ctypes.c_int
+    if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")
     ps = ctypes.POINTER(StemArgs)
     L.mcgmil_stem_args_size.restype = ctypes.c_size_t
     for name in ("mcgmil_stem_packed_size", "mcgmil_stem_workspace_size"):

@@ -25,7 +25,15 @@ instances) as one library call (mcgmil_stem_forward): an MFMA implicit GEMM stra
 bf16 instances the patcher writes, with the BatchNorm statistics accumulated in its epilogue, then
 the fused normalise + ReLU + max-pool pass. `stem_fusable` says when it applies (else the torch
 layers run); MCGMIL_NATIVE_STEM=0 switches it off.
+
+Training (opt-in, MultiHeadGatedAttentionMIL.enable_backbone_training): inside
+`native_conv_training()` `run_conv` sends a `conv32_trainable` convolution that autograd tracks to
+torch.ops.mcgmil.conv2d_f32 (mcgmil.library). `conv2d_f32_wgrad` is the HIP weight gradient
+(include/mcgmil_conv_grad.h), `conv2d_f32_dgrad` the data gradient (the forward kernel on the
+flipped weight for stride 1), `conv2d_f32_backward` the op's backward on the route
+`conv_grad_native()` names (MCGMIL_CONV_GRAD=native; default aten.convolution_backward).
 """
+import contextlib
 import ctypes
 import os
 from typing import NamedTuple, Optional
@@ -287,6 +295,194 @@ def conv2d_f32(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
     return (y, part) if stats else y
 
 
+# ---------------------------------------------------------------- fp32 convolution backward
+_native_training = False
+
+
+@contextlib.contextmanager
+def native_conv_training(flag: bool = True):
+    """Inside this context `run_conv` sends every `conv32_trainable` convolution that autograd
+    tracks to the differentiable op torch.ops.mcgmil.conv2d_f32 (forward and backward on the HIP
+    kernels). Off outside it: the opt-in of MultiHeadGatedAttentionMIL.enable_backbone_training."""
+    global _native_training
+    before, _native_training = _native_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_training = before
+
+
+def conv32_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """A convolution whose forward AND weight gradient run on the fp32 HIP kernels
+    (include/mcgmil_conv_grad.h): a CUDA channels-last fp32 activation without autocast, a
+    bias-free groups=1 dilation-1 zero-padded convolution with kernel 1..7, stride 1 or 2,
+    pad < kernel, in_channels % 16 == 0 and out_channels % 64 == 0. Says nothing about autograd:
+    that is what the kernels are for."""
+    if not (conv32_enabled() and isinstance(conv, nn.Conv2d) and x.is_cuda and x.dim() == 4):
+        return False
+    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32 or torch.is_autocast_enabled("cuda"):
+        return False
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return False
+    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
+            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
+        return False
+    kh, kw = conv.kernel_size
+    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
+        return False
+    if conv.in_channels % 16 or conv.out_channels % 64 or x.shape[1] != conv.in_channels:
+        return False
+    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
+        return False
+    s, p = _square(conv.stride), _square(conv.padding)
+    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
+    return oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256
+
+
+class _ConvShim(nn.Conv2d):
+    """The nn.Conv2d view of a bare (weight, stride, pad) triple, without nn.Conv2d's parameter
+    initialisation: what the fp32 entry points below take. The weight is shared, not copied."""
+
+    def __init__(self, weight: torch.Tensor, stride: int, pad: int):
+        nn.Module.__init__(self)
+        self.out_channels, self.in_channels = weight.shape[:2]
+        self.kernel_size = tuple(weight.shape[2:])
+        self.stride, self.padding, self.dilation = (stride, stride), (pad, pad), (1, 1)
+        self.transposed, self.output_padding, self.groups = False, (0, 0), 1
+        self.padding_mode = "zeros"
+        self.weight = nn.Parameter(weight.detach(), requires_grad=False)
+        self.register_parameter("bias", None)
+
+
+def flipped_weight(weight: torch.Tensor) -> torch.Tensor:
+    """W'[i, o, kh, kw] = W[o, i, KH-1-kh, KW-1-kw]: with it the data gradient of a stride-1
+    convolution is the forward convolution dX = conv2d(dY, W', stride 1, pad k - 1 - p)."""
+    return weight.flip(2, 3).transpose(0, 1).contiguous()
+
+
+def conv2d_f32_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
+    """dW [out, in, kh, kw] fp32 of conv(x) given dY, on the HIP weight-gradient kernel
+    (mcgmil_conv2d_wgrad_f32; see conv32_trainable). chunk_pixels caps the output pixels per
+    launch chunk (0: the library's default); the result does not depend on it, bitwise."""
+    if not conv32_trainable(conv, x):
+        raise ValueError("conv2d_f32_wgrad needs a CUDA channels-last fp32 activation and a convolution "
+                         "the weight-gradient kernel implements (see conv32_trainable)")
+    L = _lib.load()
+    g = _lib.ConvGradArgs()
+    a = g.fwd
+    a.batch, _, a.height, a.width = x.shape
+    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
+    a.kernel_h, a.kernel_w = conv.kernel_size
+    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
+    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
+    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
+    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.float32 or dy.device != x.device:
+        raise ValueError(f"dy must be fp32 {(a.batch, a.out_channels, oh, ow)} on x's device")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
+    a.x = ctypes.c_void_p(x.data_ptr())
+    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
+    g.chunk_pixels = int(chunk_pixels)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_conv_wgrad_workspace_size_f32(ctypes.byref(g), ctypes.byref(n)),
+               "mcgmil_conv_wgrad_workspace_size_f32")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
+    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(L.mcgmil_conv2d_wgrad_f32(ctypes.byref(g), stream), "mcgmil_conv2d_wgrad_f32")
+    return dw
+
+
+def dgrad_native(conv: nn.Conv2d) -> bool:
+    """Whether conv2d_f32_dgrad runs this convolution's data gradient on the forward HIP kernel:
+    stride 1 and a square kernel (one pad k - 1 - p for both axes). Stride 2 takes
+    aten.convolution_backward: there is no native strided data gradient yet."""
+    return _square(conv.stride) == 1 and conv.kernel_size[0] == conv.kernel_size[1]
+
+
+def conv2d_f32_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x_shape, x: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dX (channels-last fp32, shape x_shape) of conv(x) given dY. Stride 1: mcgmil_conv2d_f32 of
+    dY with the flipped, channel-swapped weight (flipped_weight), pad k - 1 - p; an in_channels
+    that is no multiple of 64 is padded with zero filters to the next one and cut off again.
+    Otherwise (dgrad_native False) aten.convolution_backward with output_mask (True, False,
+    False); x, when given, is passed to it as the input (only its shape and layout matter) and
+    the call is split along the batch below 2^31 bytes."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    s, p = _square(conv.stride), _square(conv.padding)
+    if dgrad_native(conv):
+        w = flipped_weight(conv.weight.detach())                      # [in, out, kh, kw]
+        cin = conv.in_channels
+        if cin % 64:
+            w = torch.cat([w, w.new_zeros((-cin % 64,) + tuple(w.shape[1:]))])
+        with torch.no_grad():
+            dx = conv2d_f32(_ConvShim(w, 1, conv.kernel_size[0] - 1 - p), dy)
+        if dx.shape[1] != cin:
+            dx = dx[:, :cin].contiguous(memory_format=torch.channels_last)
+        if tuple(dx.shape) != tuple(x_shape):
+            raise ValueError(f"x_shape {tuple(x_shape)} does not belong to this convolution and dy {tuple(dx.shape)}")
+        return dx
+    if x is not None:
+        return _aten_conv_backward(conv, x, dy, True, False)[0]
+    like = dy.new_empty(1).expand(tuple(x_shape))
+    dx = torch.ops.aten.convolution_backward(dy, like, conv.weight.detach(), None, [s, s], [p, p], [1, 1], False,
+                                             [0, 0], 1, [True, False, False])[0]
+    return dx.contiguous(memory_format=torch.channels_last)
+
+
+def conv_grad_native() -> bool:
+    """Which backward torch.ops.mcgmil.conv2d_f32 takes. MCGMIL_CONV_GRAD=native: the HIP weight
+    gradient and, for stride 1, the forward kernel as data gradient. Default ("aten"):
+    aten.convolution_backward (MIOpen) for both -- the measured-fastest for every ResNet-18 / -50
+    shape class at 64 and 256 instances ("Backbone convolution backward"); the
+    forward stays on the HIP kernel either way. Tensors of 2^31 bytes or more always take the
+    native kernels where there is one (64-bit offsets)."""
+    return os.environ.get("MCGMIL_CONV_GRAD", "aten") == "native"
+
+
+def _aten_conv_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool, need_dw: bool):
+    """(dx, dw) from aten.convolution_backward, split along the batch so that no call's x or dy
+    reaches 2^31 bytes (see torch_conv); the pieces' dw are added in batch order."""
+    s, p = _square(conv.stride), _square(conv.padding)
+    w = conv.weight.detach()
+    n = max(1, ((1 << 31) - 1) // (4 * max(x[0].numel(), dy[0].numel())))
+    dxs, dw = [], None
+    for i in range(0, x.shape[0], n):
+        gx, gw, _ = torch.ops.aten.convolution_backward(dy[i:i + n], x[i:i + n], w, None, [s, s], [p, p], [1, 1],
+                                                        False, [0, 0], 1, [need_dx, need_dw, False])
+        if need_dx:
+            dxs.append(gx)
+        if need_dw:
+            dw = gw if dw is None else dw + gw
+    dx = None
+    if need_dx:
+        dx = (dxs[0] if len(dxs) == 1 else torch.cat(dxs)).contiguous(memory_format=torch.channels_last)
+    return dx, dw.contiguous() if need_dw else None
+
+
+def conv2d_f32_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool = True,
+                        need_dw: bool = True):
+    """(dX or None, dW or None) of conv(x) given dY for a `conv32_trainable` convolution, on the
+    route conv_grad_native() names: the backward of torch.ops.mcgmil.conv2d_f32."""
+    if not conv32_trainable(conv, x):
+        raise ValueError("conv2d_f32_backward needs a convolution and activation as conv32_trainable")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    big = 4 * max(x.numel(), dy.numel()) >= 2 ** 31
+    if not (conv_grad_native() or big):
+        return _aten_conv_backward(conv, x, dy, need_dx, need_dw)
+    dw = conv2d_f32_wgrad(conv, x, dy) if need_dw else None
+    dx = None
+    if need_dx:
+        dx = conv2d_f32_dgrad(conv, dy, x.shape, x) if dgrad_native(conv) else \
+            _aten_conv_backward(conv, x, dy, True, False)[0]
+    return dx, dw
+
+
+def conv2d_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """layer(x) through the differentiable op torch.ops.mcgmil.conv2d_f32 (mcgmil.library)."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    return torch.ops.mcgmil.conv2d_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
+
+
 def _native_conv(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
     """"bf16" (conv2d), "f32" (conv2d_f32) or None (the torch layer) for conv on x."""
     if isinstance(conv, nn.Conv2d):
@@ -325,7 +521,14 @@ def torch_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
 
 def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """The backbone's convolution: the bf16 MFMA kernel when `conv_fusable`, the fp32 one when
-    `conv32_fusable`, else the torch layer."""
+    `conv32_fusable`, else the torch layer. Inside native_conv_training() a convolution under
+    autograd that is `conv32_trainable` goes to the differentiable op instead of the torch layer
+    (the activation is made channels-last first if it is not: once, after the stem)."""
+    if _native_training and isinstance(layer, nn.Conv2d) and torch.is_grad_enabled() and \
+            (x.requires_grad or layer.weight.requires_grad) and x.is_cuda and x.dim() == 4:
+        xc = x.contiguous(memory_format=torch.channels_last)
+        if conv32_trainable(layer, xc):
+            return conv2d_f32_op(layer, xc)
     if isinstance(layer, nn.Conv2d) and conv_fusable(layer, x):
         return conv2d(layer, x)
     if isinstance(layer, nn.Conv2d) and conv32_fusable(layer, x):

@@ -8,10 +8,19 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
                                    bag_id_base=0, t_base=0, need_dH=True)
                                   -> (dH [R, L] or [0, L], dWv, dbv, dWu, dbu, dwa, dba, dwk)
 
+    torch.ops.mcgmil.conv2d_f32(x, weight, stride, pad) -> y
+    torch.ops.mcgmil.conv2d_f32_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
-autograd formula, so a backward of the backward raises.
+autograd formula, so a backward of the backward raises. conv2d_f32 is the backbone's fp32
+convolution (features.conv2d_f32: x fp32 NCHW-shaped, channels-last in memory; weight
+[out, in, kh, kw]) made differentiable in x and weight the same way: its formula calls
+conv2d_f32_backward (features.conv2d_f32_backward: the HIP weight gradient and the forward kernel
+as data gradient with MCGMIL_CONV_GRAD=native, else aten.convolution_backward -- the
+measured-fastest today), which has none itself. A gradient that is not needed comes
+back as an empty tensor.
 
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
@@ -23,9 +32,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import ops
+from . import features, ops
 
-__all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward"]
+__all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -117,3 +126,66 @@ def _mcdo_forward_stats_fake(H, bag_offsets, Wv, bv, Wu, bu, wa, ba, wk, T, p_fe
     f = torch.float32
     return (H.new_empty((B, T, C), dtype=f), H.new_empty((C * R,), dtype=f),
             H.new_empty((C * R,), dtype=f), H.new_empty((B, C), dtype=f))
+
+
+def _conv_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
+    """(shim, x channels-last) for the fp32 convolution entry points, or ValueError."""
+    x = x.detach().contiguous(memory_format=torch.channels_last)
+    conv = features._ConvShim(weight, stride, pad)
+    if not features.conv32_trainable(conv, x):
+        raise ValueError("mcgmil::conv2d_f32 needs a CUDA fp32 activation and weight with kernel 1..7, "
+                         "stride 1 or 2, pad < kernel, in_channels % 16 == 0 and out_channels % 64 == 0 "
+                         "(features.conv32_trainable)")
+    return conv, x
+
+
+def _conv_out_hw(x, weight, stride, pad):
+    return ((x.shape[2] + 2 * pad - weight.shape[2]) // stride + 1,
+            (x.shape[3] + 2 * pad - weight.shape[3]) // stride + 1)
+
+
+@torch.library.custom_op("mcgmil::conv2d_f32", mutates_args=())
+def conv2d_f32(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    with torch.no_grad():
+        conv, xc = _conv_shim(x, weight, stride, pad)
+        return features.conv2d_f32(conv, xc)
+
+
+@conv2d_f32.register_fake
+def _conv2d_f32_fake(x, weight, stride, pad):
+    oh, ow = _conv_out_hw(x, weight, stride, pad)
+    return torch.empty((x.shape[0], weight.shape[0], oh, ow), dtype=torch.float32, device=x.device,
+                       memory_format=torch.channels_last)
+
+
+@torch.library.custom_op("mcgmil::conv2d_f32_backward", mutates_args=())
+def conv2d_f32_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
+                        need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        conv, xc = _conv_shim(x, weight, stride, pad)
+        dx, dw = features.conv2d_f32_backward(conv, xc, dy.detach(), need_dx, need_dw)
+    return (dx if need_dx else x.new_empty((0,))), (dw if need_dw else weight.new_empty((0,)))
+
+
+@conv2d_f32_backward.register_fake
+def _conv2d_f32_backward_fake(x, weight, dy, stride, pad, need_dx, need_dw):
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last) \
+        if need_dx else x.new_empty((0,))
+    dw = weight.new_empty(weight.shape, dtype=torch.float32) if need_dw else weight.new_empty((0,))
+    return dx, dw
+
+
+def _conv_setup_context(ctx, inputs, output):
+    x, weight, stride, pad = inputs
+    ctx.save_for_backward(x, weight)
+    ctx.geometry = (stride, pad)
+
+
+def _conv_backward(ctx, dy):
+    x, weight = ctx.saved_tensors
+    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dx, dw = torch.ops.mcgmil.conv2d_f32_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
+    return dx if need_dx else None, dw if need_dw else None, None, None
+
+
+conv2d_f32.register_autograd(_conv_backward, setup_context=_conv_setup_context)

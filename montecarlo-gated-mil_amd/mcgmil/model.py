@@ -16,8 +16,10 @@ What differs, by design:
     cross_validation.py) is opt-in: after enable_head_training(), forward() in train mode runs the
     backbone under torch autograd and the head through the differentiable op
     torch.ops.mcgmil.mcdo_forward, whose HIP backward (include/mcgmil_grad.h) draws the dropout
-    masks again instead of storing them. Without the opt-in, forward() in train mode raises
-    instead of silently running elsewhere.
+    masks again instead of storing them. enable_backbone_training() on top of it moves the
+    backbone's block convolutions from the torch layers to the differentiable fp32 HIP op
+    (torch.ops.mcgmil.conv2d_f32; include/mcgmil_conv_grad.h is its native backward). Without the opt-in, forward() in train mode raises instead of
+    silently running elsewhere.
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
 """
@@ -25,7 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import features, ops
 from .resnet import Identity, build_backbone
 
 __all__ = ["MultiHeadGatedAttentionMIL", "AuxiliaryLoss"]
@@ -95,6 +97,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self.compute_dtype = torch.float32
         self._head_cache = None
         self._head_training = False
+        self._backbone_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -230,6 +233,18 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_training = bool(flag)
         return self
 
+    def enable_backbone_training(self, flag=True):
+        """With enable_head_training(): forward() in train mode runs the backbone's block
+        convolutions (every features.conv32_trainable one: all but the 3-channel stem) through
+        the differentiable op torch.ops.mcgmil.conv2d_f32 instead of the torch layer: the fp32
+        MFMA forward kernel, and for the backward the route features.conv_grad_native() names
+        (MCGMIL_CONV_GRAD=native: the HIP weight gradient and the forward kernel again as the
+        stride-1 data gradient; default: aten.convolution_backward, which measured faster on
+        every ResNet shape class). The stem, BatchNorm, ReLU, the pools and the
+        residual add stay on the torch layers. Off by default; returns self."""
+        self._backbone_training = bool(flag)
+        return self
+
     def _live_head(self):
         """The head parameters stacked for the kernel WITH their autograd history."""
         lv, lu = self._gate_linears()
@@ -278,7 +293,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                 raise NotImplementedError("training is out of scope for the MI355X MCDO build; "
                                           "call forward() in eval mode or under torch.no_grad() "
                                           "(or opt in with enable_head_training())")
-            H = self.extract_features(x)
+            with features.native_conv_training(self._backbone_training):
+                H = self.extract_features(x)
             Y, A = self.forward_features(H, T=1, seed=seed)
             Y, A = Y[0], A[0]
             aux = None
