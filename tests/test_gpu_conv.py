@@ -51,15 +51,97 @@ SHAPES = [
     (3, 128, 13, 11, 256, 1, 2, 0),
     (2, 64, 9, 7, 192, 1, 2, 0),
     (1, 256, 14, 14, 512, 1, 2, 0),
+    # 1x1 / stride 1 from 64 channels: one K step per tile (KT == 1), so conv_dma_kernel's stream
+    # changes tile at every step (setup(), the issue cursor and the epilogue all fire each step).
+    # 134,848 pixels = 527 tiles of 256, 2-3 per workgroup row on 256 CUs, on the 256 x 64, the
+    # 256 x 128 and the 256 x 256 tiles (the last one ResNet-50's layer-1 downsample)
+    (43, 64, 56, 56, 64, 1, 1, 0),
+    (43, 64, 56, 56, 128, 1, 1, 0),
+    (43, 64, 56, 56, 256, 1, 1, 0),
+    # ResNet-50's bottleneck 1x1 / stride 1 shapes (Cin and Cout up to 2048) at ragged pixel counts
+    (3, 256, 9, 7, 64, 1, 1, 0),
+    (3, 256, 9, 7, 128, 1, 1, 0),
+    (2, 128, 9, 7, 512, 1, 1, 0),
+    (2, 512, 9, 7, 128, 1, 1, 0),
+    (2, 256, 7, 5, 1024, 1, 1, 0),
+    (2, 1024, 7, 5, 256, 1, 1, 0),
+    (2, 512, 5, 3, 2048, 1, 1, 0),
+    (2, 2048, 5, 3, 512, 1, 1, 0),
+    # its stride-2 shapes: the downsamples of layers 3 and 4 and the 3x3 of each stage's first block
+    (2, 512, 9, 7, 1024, 1, 2, 0),
+    (2, 1024, 6, 5, 2048, 1, 2, 0),
+    (2, 128, 13, 11, 128, 3, 2, 1),
+    (2, 256, 9, 7, 256, 3, 2, 1),
+    (2, 512, 7, 5, 512, 3, 2, 1),
+    # 8 channel tiles of 256 with more pixel tiles (35) than workgroup rows (32 on 256 CUs); 8 K
+    # steps, too few for a K split of the 3 tiles left
+    (180, 512, 7, 7, 2048, 1, 1, 0),
 ]
 
 
 def _layer(cin, cout, k, s, p, dev, seed):
+    """k: the window, an int or (kh, kw)."""
+    kh, kw = (k, k) if isinstance(k, int) else k
     g = torch.Generator().manual_seed(seed)
     conv = nn.Conv2d(cin, cout, k, s, p, bias=False)
     with torch.no_grad():
-        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin * k * k)) ** 0.5)
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin * kh * kw)) ** 0.5)
     return conv.to(dev).eval()
+
+
+def _planned(conv, x, flags=0):
+    """(statistics rows, K-split workspace bytes) of the launch plan, as the ABI reports them."""
+    import ctypes
+    from mcgmil import _lib
+    from mcgmil.features import _conv_args
+    a = _conv_args(conv, x)
+    a.flags = flags
+    parts, nb = ctypes.c_int32(), ctypes.c_size_t()
+    assert _lib.load().mcgmil_conv_stats_parts(ctypes.byref(a), ctypes.byref(parts)) == 0
+    assert _lib.load().mcgmil_conv_workspace_size(ctypes.byref(a), ctypes.byref(nb)) == 0
+    return parts.value, nb.value
+
+
+def _expected_plan(conv, x, cus, policy="auto"):
+    """What the tile policy is documented to pick (mcgmil_features.h), as far as the
+    ABI shows it: (256 x 256 or 512 x 128 tiles?, K split of their last round?). The 256 x 256
+    tiles take every layer with Cout % 256 == 0 (under `big512` the 512 x 128 tiles the other
+    layers with Cout % 128 == 0) except, under the auto policy, the streaming 1x1 / stride 2 from
+    64 channels and, unless `nohalo`, the 3x3 / stride 1 halo kernel with streamed weights
+    (Cin >= 128, OW >= 20, a patch of <= 480 pixels); `small` keeps the 256 x 128 tiles. The R
+    256 x 256 tiles left after F whole rounds over gb workgroup rows are cut into
+    P = min(gb // R, 4) K ranges when F >= 1, P >= 2 and there are >= 4 P K steps."""
+    N, Cin, H, W = x.shape
+    Cout, (kh, kw), s, p = conv.out_channels, conv.kernel_size, conv.stride[0], conv.padding[0]
+    oh, ow = (H + 2 * p - kh) // s + 1, (W + 2 * p - kw) // s + 1
+    wide = Cout % 256 == 0 or (policy == "big512" and Cout % 128 == 0)
+    if policy == "small" or not wide:
+        return False, False
+    if policy == "auto" and (kh, kw, s, p, Cin) == (1, 1, 2, 0, 64):
+        return False, False
+    if policy != "nohalo" and (kh, kw, s, p) == (3, 3, 1, 1) and Cin >= 128 and ow >= 20:
+        rows = (255 + ow - 1) // ow + 1
+        imgs = (255 + oh * ow - 1) // (oh * ow) + 1
+        if (rows + 2 + 2 * (imgs - 1)) * (W + 2) <= 480:
+            return False, False
+    if Cout % 256:
+        return True, False            # 512 x 128 tiles: no K split
+    tiles_m, tiles_n = (N * oh * ow + 255) // 256, Cout // 256
+    gb = min(max(cus // tiles_n, 1), tiles_m)
+    F_, R = tiles_m // gb, tiles_m % gb
+    P = min(gb // R, 4) if R else 0
+    return True, F_ >= 1 and P >= 2 and kh * kw * (Cin // 64) >= 4 * P
+
+
+def _assert_plan(conv, x, policy="auto"):
+    """The shape runs the kernel its comment names: no statistics rows exactly on the 256 x 256 and
+    512 x 128 tiles, a workspace exactly where the last round of 256 x 256 tiles is split."""
+    from mcgmil import _lib
+    cus = torch.cuda.get_device_properties(x.device).multi_processor_count
+    big, split = _expected_plan(conv, x, cus, policy)
+    parts, nb = _planned(conv, x, _lib.CONV_TILE_FLAGS[policy])
+    assert (parts == 0) == big, (policy, parts, big)
+    assert (nb > 0) == split, (policy, nb, split)
 
 
 @pytest.mark.parametrize("shape", SHAPES)
@@ -73,6 +155,7 @@ def test_conv2d_matches_fp64(cuda, shape):
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         assert conv_fusable(conv, x)
         y = conv2d(conv, x)
+    _assert_plan(conv, x)
     assert y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=torch.channels_last)
     wb = conv.weight.detach().bfloat16().double()
     with torch.no_grad():
@@ -83,8 +166,41 @@ def test_conv2d_matches_fp64(cuda, shape):
     assert torch.all(err <= 2.0 ** -8 * ref.abs() + 1e-5 * mag), float((err / (ref.abs() + 1e-30)).max())
 
 
+# kernels with kernel_h != kernel_w (conv_fusable admits them; ConvGeom keeps KH and KW apart): the
+# tap order kt = (kh KW + kw) Cin / 64 + cc, the tap mask's bit kh KW + kw and the packed weight's
+# [Cout, KH, KW, Cin] must agree. One padding for both axes, so with pad 1 a 1 x 3 window also reads
+# the rows of padding above and below the image. 495-605 pixels: 2-3 tiles, the last one ragged.
+NONSQUARE = [(kk, p, c) for kk in ((1, 3), (3, 1), (1, 7)) for p in (0, 1)
+             for c in ((64, 64), (64, 192), (128, 128))]
+
+
+@pytest.mark.parametrize("kk,p,chan", NONSQUARE)
+def test_conv2d_nonsquare_window(cuda, kk, p, chan):
+    from mcgmil.features import conv2d, conv_fusable
+    Cin, Cout = chan
+    conv = _layer(Cin, Cout, kk, 1, p, cuda, Cin + Cout + 10 * kk[0] + kk[1])
+    g = torch.Generator(device=cuda).manual_seed(Cout + kk[1] + p)
+    x = torch.randn(5, Cin, 9, 11, device=cuda, generator=g).relu_().bfloat16()
+    x = x.contiguous(memory_format=torch.channels_last)
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
+        assert conv_fusable(conv, x)
+        y = conv2d(conv, x)
+        assert torch.equal(conv2d(conv, x), y)
+    _assert_plan(conv, x)
+    wb = conv.weight.detach().bfloat16().double()
+    with torch.no_grad():
+        ref = F.conv2d(x.double(), wb, None, 1, p)
+        mag = F.conv2d(x.double().abs(), wb.abs(), None, 1, p)
+    assert y.shape == ref.shape
+    err = (y.double() - ref).abs()
+    assert torch.all(err <= 2.0 ** -8 * ref.abs() + 1e-5 * mag), float((err / (ref.abs() + 1e-30)).max())
+
+
 TILE_SHAPES = [(3, 64, 56, 56, 64, 3, 1, 1), (3, 128, 28, 28, 128, 3, 1, 1), (2, 256, 14, 14, 512, 3, 2, 1),
-               (2, 64, 9, 7, 192, 1, 2, 0)]
+               (2, 64, 9, 7, 192, 1, 2, 0),
+               # one K step per tile, 2-3 tiles per workgroup row; under `small` the 256-channel one
+               # takes the 256 x 128 tiles
+               (43, 64, 56, 56, 64, 1, 1, 0), (43, 64, 56, 56, 128, 1, 1, 0), (43, 64, 56, 56, 256, 1, 1, 0)]
 
 
 @pytest.mark.parametrize("shape", TILE_SHAPES)
@@ -110,14 +226,20 @@ def test_conv2d_tile_policy_flags(cuda, shape):
         assert torch.equal(y, y2), name
         err = (y.double() - ref).abs()
         assert torch.all(err <= 2.0 ** -8 * ref.abs() + 1e-5 * mag), name
+        _assert_plan(conv, x, name)
 
 
 # 256 x 256 tiles with a short last round (on 256 CUs: 14 x 14 -> 256, 307 tiles over 256 rows, 51
 # left in 4 K ranges; 7 x 7 x 512 and its stride-2 producer, 134 tiles over 128 rows, 6 left in 4)
 SPLIT_SHAPES = [(400, 256, 14, 14, 256, 3, 1, 1), (700, 512, 7, 7, 512, 3, 1, 1), (700, 256, 14, 14, 512, 3, 2, 1)]
+# ResNet-50's layer 4 on 256 CUs: a 1x1 / stride 2 window into 8 channel tiles (35 tiles over 32 rows,
+# 3 left in 4 ranges of the 16 K steps: slot (tn R + q) P + pp at tn up to 7), and 1x1 / stride 1
+# from 2048 channels (134 tiles over 128 rows, 6 left in 4 ranges of the 32 K steps). These two must
+# split on the device the suite runs on: a skip would let them pass without the split.
+SPLIT_SHAPES_R50 = [(180, 1024, 14, 14, 2048, 1, 2, 0), (700, 2048, 7, 7, 512, 1, 1, 0)]
 
 
-@pytest.mark.parametrize("shape", SPLIT_SHAPES)
+@pytest.mark.parametrize("shape", SPLIT_SHAPES + SPLIT_SHAPES_R50)
 def test_conv2d_k_split(cuda, shape, monkeypatch):
     """The K split of the last round of 256 x 256 tiles (mcgmil_conv_args.workspace): within the
     fp64 bound and repeatable; the whole tiles bitwise those of the unsplit launch
@@ -132,6 +254,9 @@ def test_conv2d_k_split(cuda, shape, monkeypatch):
     x = x.contiguous(memory_format=torch.channels_last)
     nb = ctypes.c_size_t()
     assert _lib.load().mcgmil_conv_workspace_size(ctypes.byref(_conv_args(conv, x)), ctypes.byref(nb)) == 0
+    if shape in SPLIT_SHAPES_R50:
+        assert nb.value > 0
+        _assert_plan(conv, x)
     if nb.value == 0:
         pytest.skip("no K split for this shape at this GPU's CU count")
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
@@ -295,6 +420,15 @@ STATS_SHAPES = [
     # channel blocks, the stream count rounded up to 2 -- an empty stream whose statistics rows have
     # count 0 and must merge away in the BN finalize
     (1, 64, 6, 6, 192, 1, 2, 0, 0.0),
+    # ResNet-50's bottleneck shapes: 1x1 / stride 1 on the 256 x 64 tiles (4 K steps, a single ragged
+    # tile, with and without an input offset), one K step per tile with 2-3 tiles per statistics
+    # row on the 256 x 128 tiles, the 256 x 256 tiles that emit no statistics (the BN then makes
+    # its own pass, at C = 2048), and a 3x3 / stride 2
+    (3, 256, 9, 7, 64, 1, 1, 0, 0.0),
+    (3, 256, 9, 7, 64, 1, 1, 0, 2.0),
+    (43, 64, 56, 56, 128, 1, 1, 0, 0.0),
+    (2, 512, 5, 3, 2048, 1, 1, 0, 0.0),
+    (2, 128, 13, 11, 128, 3, 2, 1, 0.0),
 ]
 
 
@@ -316,6 +450,7 @@ def test_conv_bn_act_fused_statistics(cuda, shape, residual):
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         y = conv_bn_act(conv, bn, x, True, idt)
         _, part = conv2d(conv, x, stats=True)
+    _assert_plan(conv, x)
     if part is not None:            # the 256 x 256 tiles (Cout % 256 == 0) emit none
         assert part.shape[1:] == (3, Cout)
         assert float(part[:, 0, :].sum(0).min()) == N * oh * ow == float(part[:, 0, :].sum(0).max())
@@ -445,21 +580,29 @@ def test_backbone_input_bn_bitwise(cuda):
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-def test_residual_bn_bitwise_equals_unfused(cuda, dtype):
+def test_residual_bn_bitwise_equals_unfused(cuda, dtype, C=128):
     """batchnorm_act(y, bn2, relu, residual=r, residual_ab=ab_d) equals normalising r in a pass of
     its own first (the downsample branch), bit for bit."""
     from mcgmil.features import batchnorm_act, batchnorm_coefficients
-    bn2, bnd = _bn64(128, cuda, 11), _bn64(128, cuda, 12)
+    bn2, bnd = _bn64(C, cuda, 11), _bn64(C, cuda, 12)
     g = torch.Generator(device=cuda).manual_seed(3)
-    y = (torch.randn(5, 128, 14, 13, device=cuda, generator=g) * 3 + 1).to(dtype).contiguous(
+    y = (torch.randn(5, C, 14, 13, device=cuda, generator=g) * 3 + 1).to(dtype).contiguous(
         memory_format=torch.channels_last)
-    r = (torch.randn(5, 128, 14, 13, device=cuda, generator=g) * 2 - 1).to(dtype).contiguous(
+    r = (torch.randn(5, C, 14, 13, device=cuda, generator=g) * 2 - 1).to(dtype).contiguous(
         memory_format=torch.channels_last)
     with torch.no_grad():
         ab_d = batchnorm_coefficients(r, bnd)
         ref = batchnorm_act(y, bn2, True, residual=batchnorm_act(r, bnd, False))
         out = batchnorm_act(y, bn2, True, residual=r, residual_ab=ab_d)
     assert torch.equal(out, ref)
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_residual_bn_bitwise_equals_unfused_c200(cuda, dtype):
+    """The same at 200 channels: 25 channel groups do not divide a workgroup's 256 threads, so the
+    apply grid is rounded to a multiple of 25 blocks for a thread to keep its a, b and the
+    residual's own a, b."""
+    test_residual_bn_bitwise_equals_unfused(cuda, dtype, C=200)
 
 
 def test_backbone_running_statistics_folds_bitwise(cuda):

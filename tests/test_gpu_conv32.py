@@ -33,14 +33,36 @@ SHAPES = [
     (3, 3, 64, 52, 64, 7, 2, 3),
     (2, 5, 17, 9, 128, 5, 1, 2),
     (4, 24, 6, 7, 64, 1, 1, 0),
+    # ResNet-50's bottleneck shapes at ragged pixel counts: 1x1 / stride 1 with Cin and Cout up to
+    # 2048 (128 K steps), its stride-2 downsamples and 3x3s, and layer 1's 1x1 from 64 channels
+    # at 527 pixel tiles
+    (3, 256, 9, 7, 64, 1, 1, 0),
+    (3, 256, 9, 7, 128, 1, 1, 0),
+    (2, 128, 9, 7, 512, 1, 1, 0),
+    (2, 512, 9, 7, 128, 1, 1, 0),
+    (2, 256, 7, 5, 1024, 1, 1, 0),
+    (2, 1024, 7, 5, 256, 1, 1, 0),
+    (2, 512, 5, 3, 2048, 1, 1, 0),
+    (2, 2048, 5, 3, 512, 1, 1, 0),
+    (2, 512, 9, 7, 1024, 1, 2, 0),
+    (2, 1024, 6, 5, 2048, 1, 2, 0),
+    (2, 128, 13, 11, 128, 3, 2, 1),
+    (2, 256, 9, 7, 256, 3, 2, 1),
+    (2, 512, 7, 5, 512, 3, 2, 1),
+    (43, 64, 56, 56, 64, 1, 1, 0),
+    # a single K step of 16 (1x1 from 16 channels) on both tile shapes, 315 pixels
+    (5, 16, 9, 7, 64, 1, 1, 0),
+    (5, 16, 9, 7, 128, 1, 1, 0),
 ]
 
 
 def _layer(cin, cout, k, s, p, dev, seed):
+    """k: the window, an int or (kh, kw)."""
+    kh, kw = (k, k) if isinstance(k, int) else k
     g = torch.Generator().manual_seed(seed)
     conv = nn.Conv2d(cin, cout, k, s, p, bias=False)
     with torch.no_grad():
-        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin * k * k)) ** 0.5)
+        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin * kh * kw)) ** 0.5)
     return conv.to(dev).eval()
 
 
@@ -71,6 +93,28 @@ def test_conv2d_f32_matches_fp64(cuda, shape):
         _check(y, x, conv)
         _check(conv(x), x, conv)                   # MIOpen's fp32 convolution, the same bound
         # repeatable: the same bits from a second launch
+        assert torch.equal(conv2d_f32(conv, x), y)
+
+
+# kernel_h != kernel_w (conv32_fusable admits them): the K step's tap -> (kh, kw) = (tap / KW,
+# tap % KW) in the kernel and in the weight packing; one padding for both axes
+NONSQUARE = [(kk, p, c) for kk in ((1, 3), (3, 1), (1, 7)) for p in (0, 1)
+             for c in ((64, 64), (64, 192), (128, 128))]
+
+
+@pytest.mark.parametrize("kk,p,chan", NONSQUARE)
+def test_conv2d_f32_nonsquare_window(cuda, kk, p, chan):
+    from mcgmil.features import conv2d_f32, conv32_fusable
+    Cin, Cout = chan
+    conv = _layer(Cin, Cout, kk, 1, p, cuda, Cin + Cout + 10 * kk[0] + kk[1])
+    g = torch.Generator(device=cuda).manual_seed(Cout + kk[1] + p)
+    x = torch.randn(5, Cin, 9, 11, device=cuda, generator=g).contiguous(memory_format=torch.channels_last)
+    with torch.no_grad():
+        assert conv32_fusable(conv, x)
+        y = conv2d_f32(conv, x)
+        torch.cuda.synchronize()
+        assert y.shape == conv(x).shape
+        _check(y, x, conv)
         assert torch.equal(conv2d_f32(conv, x), y)
 
 
@@ -152,7 +196,10 @@ def test_conv2d_f32_stats(cuda, shape):
 
 @pytest.mark.parametrize("relu", [True, False])
 @pytest.mark.parametrize("shape", [(3, 64, 15, 11, 64, 3, 1, 1), (2, 128, 9, 9, 256, 3, 2, 1),
-                                   (2, 64, 12, 12, 128, 1, 2, 0)])
+                                   (2, 64, 12, 12, 128, 1, 2, 0),
+                                   # ResNet-50's 1x1 / stride 1: Cin at the 2048-channel limit of the
+                                   # a, b table in LDS (128 x 128 tiles), and the 64 x 256 tiles
+                                   (2, 2048, 5, 3, 512, 1, 1, 0), (3, 256, 9, 7, 64, 1, 1, 0)])
 def test_conv2d_f32_input_bn_bitwise(cuda, shape, relu):
     """conv(relu?(bn(x))) with the BatchNorm applied while staging (in_ab) is bit-identical to
     mcgmil_batchnorm_act followed by the plain convolution -- padding stays zero."""

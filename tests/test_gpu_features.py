@@ -43,7 +43,12 @@ def _bn(C, dev, seed):
     return bn.to(dev)
 
 
-SHAPES = [(4, 64, 56, 56), (3, 128, 28, 28), (2, 512, 7, 7), (5, 8, 3, 5), (1, 2048, 2, 3)]
+# the last four: channel counts whose C / 8 does not divide the 256 threads of a workgroup (3, 25,
+# 127 and 255 channel groups) -- the apply / pool grids are rounded to a multiple of
+# CG / gcd(CG, 256) blocks so that a thread keeps its channel group, and the statistics pass has
+# 256 - (256 / CG) CG idle threads (1, 6, 2 and 1)
+SHAPES = [(4, 64, 56, 56), (3, 128, 28, 28), (2, 512, 7, 7), (5, 8, 3, 5), (1, 2048, 2, 3),
+          (3, 24, 5, 7), (2, 200, 9, 3), (3, 1016, 3, 5), (1, 2040, 2, 3)]
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -100,9 +105,29 @@ def test_bn_act_many_rows_deterministic(cuda):
     assert torch.all((y1.double() - ref).abs() <= 2.0 ** -8 * ref.abs() + 1e-5)
 
 
+def test_bn_act_many_rows_idle_lanes_deterministic(cuda):
+    """70,000 rows of 24 channels: 52 statistics workgroups of 85 row lanes x 3 channel groups (one
+    thread idle in each) and an apply grid rounded to a multiple of 3 blocks: matches torch and is
+    bitwise repeatable."""
+    from mcgmil.features import batchnorm_act
+    from mcgmil.resnet import deactivate_batchnorm
+    bn = _bn(24, cuda, 10)
+    deactivate_batchnorm(bn)
+    g = torch.Generator(device=cuda).manual_seed(24)
+    x = (torch.randn(7, 24, 100, 100, device=cuda, generator=g) * 2 + 5).bfloat16().contiguous(
+        memory_format=torch.channels_last)
+    with torch.no_grad():
+        y1 = batchnorm_act(x, bn, True)
+        y2 = batchnorm_act(x, bn, True)
+        ref = _ref(x, bn, True, None, True)
+    assert torch.equal(y1, y2)
+    assert torch.all((y1.double() - ref).abs() <= 2.0 ** -8 * ref.abs() + 1e-5)
+
+
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("shape,kpd", [((3, 64, 112, 112), (3, 2, 1)), ((2, 64, 7, 9), (3, 2, 1)),
-                                       ((2, 16, 8, 6), (2, 2, 0)), ((1, 32, 5, 5), (3, 1, 1))])
+                                       ((2, 16, 8, 6), (2, 2, 0)), ((1, 32, 5, 5), (3, 1, 1)),
+                                       ((2, 24, 9, 7), (3, 2, 1)), ((3, 200, 7, 5), (3, 2, 1))])
 def test_bn_act_maxpool_matches_torch(cuda, shape, kpd, dtype):
     """The stem: maxpool(relu(bn(x))) fused equals torch's pooling of the rounded activations."""
     from mcgmil.features import batchnorm_act
