@@ -482,10 +482,14 @@ int gate_params(const mcgmil_args* a, mcgmil::GateParams& gp) {
     gp.bu = a->bu;
     gp.wa = a->wa;
     gp.ba = a->ba;
-    gp.sf = dropout_scale(a->p_feat);
-    gp.sa = dropout_scale(a->p_att);
     gp.thr_f = drop_threshold(a->p_feat);
     gp.thr_a = drop_threshold(a->p_att);
+    // 1 - 2^-17 <= p_feat < 1: the threshold rounds to 65536, which drops every feature, while
+    // 1 / (1 - p) is still finite. The packed keep rule compares 16-bit halves, so its threshold
+    // stops at 65535 and a draw equal to 0xFFFF would survive it: the features are zeroed through
+    // their scale instead, as for p = 1 (with nothing kept the two are the same arithmetic).
+    gp.sf = gp.thr_f >= 65536u ? 0.0f : dropout_scale(a->p_feat);
+    gp.sa = dropout_scale(a->p_att);
     gp.thrx_f = mcgmil::packed_threshold(gp.thr_f);
     gp.k0 = (uint32_t)a->seed;
     gp.k1 = (uint32_t)(a->seed >> 32);

@@ -42,7 +42,8 @@ __device__ __forceinline__ uint4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
 
 // Packed form of the keep rule for the two 16-bit draws of one Philox word: returns 0xFFFF in
 // each half whose draw is DROPPED (u16 < thr) and 0 where it is kept. thrx = the threshold
-// (clamped to 65535; p = 1 is handled by the zero dropout scale) with its sign bit flipped, in
+// (clamped to 65535; a threshold of 65536, p >= 1 - 2^-17, is handled by the host's zero feature
+// scale, gate_params in mcgmil.hip) with its sign bit flipped, in
 // both halves: u >= thr (unsigned) <=> (u ^ 0x8000) >= (thr ^ 0x8000) (signed), and a
 // saturating signed difference keeps the sign. v_xor + v_pk_sub_i16 clamp + v_pk_ashrrev_i16.
 typedef short s16x2 __attribute__((ext_vector_type(2)));

@@ -15,6 +15,7 @@ import torch
 
 import golden_util
 import head_grad_ref as ref
+import head_regimes as hr
 from mcgmil import MultiHeadGatedAttentionMIL, _lib, ops, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -24,15 +25,23 @@ TILE = 32                       # rows of a grad_rows_kernel tile at L = 512, D 
 # one bag over three split-K granules, the last one ragged, and a ragged last row tile
 N_SPLITK = 2 * GRAN + 2 * TILE + 12
 
+PLAIN = (1, 1, 1)               # torch's default init: gates in their linear part, flat attention
 CASES = {
-    #           sizes              T  C  D    shared p_f  p_a  t_base bag_ids
-    "n1":      ((1,),              1, 2, 128, False, 0.1, 0.1, 0, None),
-    "n37":     ((37,),             1, 2, 128, True,  0.1, 0.1, 0, None),
-    "n130":    ((130,),            2, 3, 64,  False, 0.1, 0.1, 0, None),
-    "ragged":  ((1, 70, 129, 16),  3, 2, 128, False, 0.1, 0.1, 5, (7, 3, 11, 5)),
-    "p0":      ((70,),             2, 2, 128, False, 0.0, 0.0, 0, None),
-    "p05":     ((70,),             2, 2, 128, True,  0.5, 0.5, 0, None),
-    "splitk":  ((N_SPLITK,),       2, 2, 128, False, 0.1, 0.1, 0, None),
+    #           sizes              T  C  D    shared p_f  p_a  t_base bag_ids  (gv, gu, ga)  features
+    "n1":      ((1,),              1, 2, 128, False, 0.1, 0.1, 0, None, PLAIN, "relu"),
+    "n37":     ((37,),             1, 2, 128, True,  0.1, 0.1, 0, None, PLAIN, "relu"),
+    "n130":    ((130,),            2, 3, 64,  False, 0.1, 0.1, 0, None, PLAIN, "relu"),
+    "ragged":  ((1, 70, 129, 16),  3, 2, 128, False, 0.1, 0.1, 5, (7, 3, 11, 5), PLAIN, "relu"),
+    "p0":      ((70,),             2, 2, 128, False, 0.0, 0.0, 0, None, PLAIN, "relu"),
+    "p05":     ((70,),             2, 2, 128, True,  0.5, 0.5, 0, None, PLAIN, "relu"),
+    "splitk":  ((N_SPLITK,),       2, 2, 128, False, 0.1, 0.1, 0, None, PLAIN, "relu"),
+    # tests/head_regimes.py: peaked attention and gates out of their linear part, where the gate
+    # gradients weigh against dwk (float64: max|dWv| 1.5, max|dWu| 0.45 against max|dwk| 3.8 in
+    # "trained", 2.9 and 1.1 against 8.5 in "trained_ragged"; 0.03 against 1.07 in the cases above)
+    "trained": ((70,),             2, 2, 128, False, 0.1, 0.1, 0, None, hr.REGIMES["trained"], "relu"),
+    "trained_ragged": ((1, 70, 129, 16), 3, 2, 128, False, 0.1, 0.1, 5, (7, 3, 11, 5),
+                       hr.REGIMES["trained"], "signed_sparse"),
+    "saturated_peaked": ((70,),    2, 2, 128, True,  0.1, 0.1, 0, None, hr.REGIMES["saturated_peaked"], "relu"),
 }
 SEED = 0x1234567890ABCDEF
 
@@ -45,13 +54,13 @@ class Case:
 def case(name, dev_index=0):
     """Inputs, the forward call's A and Y, the kernel's masks, and the float64 / fp32 CPU
     reference gradients for loss = sum(Y dY) + sum(A dA): computed once, never modified."""
-    sizes, T, C, D, shared, p_f, p_a, t_base, bag_ids = CASES[name]
+    sizes, T, C, D, shared, p_f, p_a, t_base, bag_ids, gains, kind = CASES[name]
     dev = torch.device("cuda", dev_index)
     c = Case()
     c.name, c.sizes, c.T, c.C, c.D, c.shared, c.p_f, c.p_a, c.t_base = name, sizes, T, C, D, shared, p_f, p_a, t_base
     L, R, B = 512, sum(sizes), len(sizes)
-    c.Hn = np.concatenate([synthetic.bag_features(100 + b, n, L) for b, n in enumerate(sizes)])
-    sd = synthetic.head_state_dict(77, L=L, D=D, C=C, shared=shared)
+    c.Hn = np.concatenate([hr.features(kind, 100 + b, n, L) for b, n in enumerate(sizes)])
+    sd = hr.scale_state_dict(synthetic.head_state_dict(77, L=L, D=D, C=C, shared=shared), *gains)
     arrays = synthetic.head_arrays(sd, C, shared)
     c.params = [np.ascontiguousarray(arrays[k]) for k in ref.PARAMS]
     c.head = ops.HeadTensors(*[torch.from_numpy(a).to(dev) for a in c.params])
