@@ -54,6 +54,9 @@ GRAD_EXPORTED = ("mcgmil_grad_args_size", "mcgmil_grad_workspace_size", "mcgmil_
 # include/mcgmil_conv_grad.h (the fp32 convolution's weight gradient; additive as well)
 CONV_GRAD_EXPORTED = ("mcgmil_conv_grad_args_size", "mcgmil_conv_wgrad_workspace_size_f32",
                       "mcgmil_conv2d_wgrad_f32")
+# include/mcgmil_bn_grad.h (the fused BatchNorm/add/ReLU's backward; additive as well)
+BN_GRAD_EXPORTED = ("mcgmil_bn_grad_args_size", "mcgmil_bn_grad_workspace_size",
+                    "mcgmil_batchnorm_act_backward")
 
 _vp = ctypes.c_void_p
 
@@ -135,6 +138,19 @@ class ConvGradArgs(ctypes.Structure):
 
 
 WGRAD_GRANULE_PIXELS = 2048        # MCGMIL_WGRAD_GRANULE_PIXELS
+
+
+class BnGradArgs(ctypes.Structure):
+    """Mirror of struct mcgmil_bn_grad_args (include/mcgmil_bn_grad.h)."""
+    _fields_ = [
+        ("rows", ctypes.c_int64), ("channels", ctypes.c_int32), ("relu", ctypes.c_int32),
+        ("x", _vp), ("y", _vp), ("dy", _vp), ("gamma", _vp), ("mean", _vp), ("invstd", _vp),
+        ("dx", _vp), ("dresidual", _vp), ("dgamma", _vp), ("dbeta", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int64),
+    ]
+
+
+BN_GRAD_PART_ELEMS = 32768         # MCGMIL_BN_GRAD_PART_ELEMS
 
 
 class StemArgs(ctypes.Structure):
@@ -282,6 +298,15 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")
+    pbg = ctypes.POINTER(BnGradArgs)
+    L.mcgmil_bn_grad_args_size.restype = ctypes.c_size_t
+    L.mcgmil_bn_grad_workspace_size.argtypes = [pbg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_bn_grad_workspace_size.restype = ctypes.c_int
+    L.mcgmil_batchnorm_act_backward.argtypes = [pbg, _vp]
+    L.mcgmil_batchnorm_act_backward.restype = ctypes.c_int
+    if L.mcgmil_bn_grad_args_size() != ctypes.sizeof(BnGradArgs):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_grad_args)={L.mcgmil_bn_grad_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(BnGradArgs)} bytes")
     ps = ctypes.POINTER(StemArgs)
     L.mcgmil_stem_args_size.restype = ctypes.c_size_t
     for name in ("mcgmil_stem_packed_size", "mcgmil_stem_workspace_size"):

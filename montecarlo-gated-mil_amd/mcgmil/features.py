@@ -32,6 +32,11 @@ torch.ops.mcgmil.conv2d_f32 (mcgmil.library). `conv2d_f32_wgrad` is the HIP weig
 (include/mcgmil_conv_grad.h), `conv2d_f32_dgrad` the data gradient (the forward kernel on the
 flipped weight for stride 1), `conv2d_f32_backward` the op's backward on the route
 `conv_grad_native()` names (MCGMIL_CONV_GRAD=native; default aten.convolution_backward).
+Inside `native_norm_training()` (enable_backbone_training(norm=True)) `bn_act` sends a pool-free
+`bn_trainable` BatchNorm (+ residual add) (+ ReLU) that autograd tracks to
+torch.ops.mcgmil.bn_act_f32: `batchnorm_act_stats` is its forward (mcgmil_batchnorm_act, which also
+returns the batch mean and 1 / sqrt(var + eps)), `batchnorm_act_backward` its HIP backward
+(include/mcgmil_bn_grad.h).
 """
 import contextlib
 import ctypes
@@ -656,10 +661,167 @@ def batchnorm_coefficients(x: torch.Tensor, bn: nn.BatchNorm2d,
     return ab
 
 
+# ---------------------------------------------------------------- fused BatchNorm backward
+_native_norm_training = False
+
+
+@contextlib.contextmanager
+def native_norm_training(flag: bool = True):
+    """Inside this context `bn_act` sends every pool-free `bn_trainable` BatchNorm (+ residual add)
+    (+ ReLU) that autograd tracks to the differentiable op torch.ops.mcgmil.bn_act_f32 (the fused
+    HIP forward and its HIP backward, include/mcgmil_bn_grad.h). Off outside it: the opt-in of
+    MultiHeadGatedAttentionMIL.enable_backbone_training(norm=True)."""
+    global _native_norm_training
+    before, _native_norm_training = _native_norm_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_norm_training = before
+
+
+def bn_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why `bn_trainable` refuses (x, bn, residual), or None when it holds. The device is checked
+    last, so the other clauses can be seen on a machine without a GPU."""
+    if not isinstance(bn, nn.BatchNorm2d) or x.dim() != 4:
+        return "layer: an nn.BatchNorm2d on a 4-D activation"
+    if x.dtype != torch.float32 or any(p is not None and p.dtype != torch.float32 for p in (bn.weight, bn.bias)):
+        return "dtype: fp32 only"
+    C = x.shape[1]
+    if C % 8 or C > 2048 or C != bn.num_features:
+        return "channels: C % 8 == 0, C <= 2048, C == bn.num_features"
+    if x.numel() < 2 * C:
+        return "rows: at least 2 values per channel"
+    if not _use_batch(bn):
+        return "statistics: running-statistics mode"
+    if bn.training and bn.track_running_stats and bn.running_mean is not None:
+        return "statistics: a running-statistics update is pending"     # torch would update them
+    if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or
+                                 residual.device != x.device):
+        return "residual: x's shape, dtype and device"
+    if not x.is_cuda or any(p is not None and p.device != x.device for p in (bn.weight, bn.bias)):
+        return "device: a CUDA activation with the parameters on its device"
+    if torch.is_autocast_enabled("cuda"):
+        return "autocast"
+    return None
+
+
+def bn_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[torch.Tensor] = None) -> bool:
+    """A BatchNorm (+ residual add) (+ ReLU) whose forward AND backward run on the fused fp32 HIP
+    kernels: a CUDA fp32 4-D activation without autocast, C % 8 == 0, C <= 2048,
+    C == bn.num_features, at least 2 values per channel, a BN that normalises with batch
+    statistics and has no running-statistics update pending (a BN in train mode that tracks
+    running statistics keeps the torch path, which updates them, exactly as in `fusable`), and a
+    residual, if any, of x's shape and dtype. Says nothing about autograd or the memory layout
+    (`bn_act` makes the activation channels-last first). `bn_untrainable_reason` names the clause
+    that fails."""
+    return bn_untrainable_reason(x, bn, residual) is None
+
+
+def _check_rows_c(name: str, x: torch.Tensor, **like) -> None:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] % 8 == 0 and
+            x.shape[1] <= 2048 and x.numel() >= 2 * x.shape[1] and
+            x.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError(f"{name} needs a CUDA channels-last fp32 [N, C, H, W] activation with C % 8 == 0, "
+                         "C <= 2048 and at least 2 values per channel")
+    for n, t in like.items():
+        if t is not None and (t.shape != x.shape or t.dtype != x.dtype or t.device != x.device or
+                              not t.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError(f"{name}: {n} must be channels-last with x's shape, dtype and device")
+
+
+def _check_per_channel(name: str, C: int, dev, **vecs) -> None:
+    for n, t in vecs.items():
+        if t is not None and (t.shape != (C,) or t.dtype != torch.float32 or t.device != dev or
+                              not t.is_contiguous()):
+            raise ValueError(f"{name}: {n} must be a contiguous fp32 [{C}] tensor on x's device")
+
+
+def batchnorm_act_stats(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                        residual: Optional[torch.Tensor], eps: float, relu: bool):
+    """(y, mean [C], invstd [C]) of relu?(batch_norm(x) [+ residual]) on the batch statistics of x
+    (fp32, channels-last): mcgmil_batchnorm_act with batch_mean / batch_invstd requested and the
+    statistics from its own pass over x. What the backward (batchnorm_act_backward) needs."""
+    _check_rows_c("batchnorm_act_stats", x, residual=residual)
+    L = _lib.load()
+    dev = x.device
+    N, C, H, W = x.shape
+    _check_per_channel("batchnorm_act_stats", C, dev, weight=weight, bias=bias)
+    y = torch.empty_like(x, memory_format=torch.channels_last)
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    invstd = torch.empty(C, dtype=torch.float32, device=dev)
+    a = _lib.BnArgs()
+    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_F32
+    a.batch, a.height, a.width = N, H, W
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.x, a.y, a.residual = p(x), p(y), p(residual)
+    a.gamma, a.beta = p(weight), p(bias)
+    a.eps, a.relu = float(eps), int(bool(relu))
+    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+    a.workspace, a.workspace_bytes = p(ws), n.value
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), stream), "mcgmil_batchnorm_act")
+    return y, mean, invstd
+
+
+def batchnorm_act_backward(x: torch.Tensor, y: Optional[torch.Tensor], dy: torch.Tensor,
+                           weight: Optional[torch.Tensor], mean: torch.Tensor, invstd: torch.Tensor,
+                           relu: bool, need_dx: bool = True, need_dres: bool = False, need_dw: bool = True):
+    """(dx, dresidual, dweight, dbias), None where not needed, of batchnorm_act_stats given dy
+    (mcgmil_batchnorm_act_backward, include/mcgmil_bn_grad.h). y is the forward's output, read for
+    the ReLU mask only (None without ReLU). dresidual exists with ReLU only: without it the
+    residual's gradient is dy itself and the caller passes dy on."""
+    _check_rows_c("batchnorm_act_backward", x, y=y if relu else None, dy=dy)
+    if relu and y is None:
+        raise ValueError("batchnorm_act_backward: relu needs y (the forward's output)")
+    need_dres = bool(need_dres and relu)
+    if not (need_dx or need_dres or need_dw):
+        return None, None, None, None
+    L = _lib.load()
+    dev = x.device
+    N, C, H, W = x.shape
+    _check_per_channel("batchnorm_act_backward", C, dev, weight=weight, mean=mean, invstd=invstd)
+    dx = torch.empty_like(x, memory_format=torch.channels_last) if need_dx else None
+    dres = torch.empty_like(x, memory_format=torch.channels_last) if need_dres else None
+    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    a = _lib.BnGradArgs()
+    a.rows, a.channels, a.relu = N * H * W, C, int(bool(relu))
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.x, a.y, a.dy = p(x), p(y if relu else None), p(dy)
+    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
+    a.dx, a.dresidual, a.dgamma, a.dbeta = p(dx), p(dres), p(dw), p(db)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_grad_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_grad_workspace_size")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
+    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_act_backward(ctypes.byref(a), stream), "mcgmil_batchnorm_act_backward")
+    return dx, dres, dw, db
+
+
+def bn_act_f32_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu?(bn(x) [+ residual]) through the differentiable op torch.ops.mcgmil.bn_act_f32
+    (mcgmil.library); the activation and the residual are made channels-last first if they are not."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    x = x.contiguous(memory_format=torch.channels_last)
+    if residual is not None:
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    return torch.ops.mcgmil.bn_act_f32(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
+
+
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
            residual: Optional[torch.Tensor] = None, pool: Optional[nn.Module] = None) -> torch.Tensor:
     """The backbone's `pool?(relu?(bn(x) [+ residual]))`: fused on the GPU when `fusable`, else
-    the torch layers (CPU, autograd, training with running-stat updates, odd layouts)."""
+    the torch layers (CPU, autograd, training with running-stat updates, odd layouts). Inside
+    native_norm_training() a pool-free `bn_trainable` layer under autograd goes to the
+    differentiable fused op instead of the torch layers."""
+    if _native_norm_training and pool is None and torch.is_grad_enabled() and isinstance(bn, nn.BatchNorm2d) and \
+            (x.requires_grad or any(p.requires_grad for p in bn.parameters())) and bn_trainable(x, bn, residual):
+        return bn_act_f32_op(bn, x, relu, residual)
     if fusable(x, bn, residual):
         if pool is None or (residual is None and _pool_params(pool) is not None):
             return batchnorm_act(x, bn, relu, residual, pool)

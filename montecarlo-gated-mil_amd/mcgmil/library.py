@@ -11,6 +11,10 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.conv2d_f32(x, weight, stride, pad) -> y
     torch.ops.mcgmil.conv2d_f32_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
 
+    torch.ops.mcgmil.bn_act_f32(x, weight?, bias?, residual?, eps, relu) -> (y, mean, invstd)
+    torch.ops.mcgmil.bn_act_f32_backward(x, y, dy, weight?, mean, invstd, relu, need_dx, need_dres,
+                                         need_dw) -> (dx, dres, dweight, dbias)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -21,6 +25,16 @@ conv2d_f32_backward (features.conv2d_f32_backward: the HIP weight gradient and t
 as data gradient with MCGMIL_CONV_GRAD=native, else aten.convolution_backward -- the
 measured-fastest today), which has none itself. A gradient that is not needed comes
 back as an empty tensor.
+
+bn_act_f32 is the blocks' relu?(batch_norm(x) [+ residual]) on the batch statistics of x (fp32,
+x NCHW-shaped and channels-last in memory, made so if it is not): the fused forward
+features.batchnorm_act_stats, which also returns the per-channel mean and 1 / sqrt(var + eps) it
+used. It is differentiable in x, weight, bias and residual; its formula saves x, weight, mean,
+invstd (and y for the ReLU mask) and calls bn_act_f32_backward (features.batchnorm_act_backward,
+include/mcgmil_bn_grad.h), which has no formula itself. mean and invstd are returned for that
+backward: gradients flowing into them are ignored (they are not differentiable outputs). Without
+ReLU the residual's gradient is dy itself: bn_act_f32_backward then returns an empty dres and the
+formula passes dy on.
 
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
@@ -34,7 +48,8 @@ import torch
 
 from . import features, ops
 
-__all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward"]
+__all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
+           "bn_act_f32", "bn_act_f32_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -189,3 +204,73 @@ def _conv_backward(ctx, dy):
 
 
 conv2d_f32.register_autograd(_conv_backward, setup_context=_conv_setup_context)
+
+
+def _channels_last(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().contiguous(memory_format=torch.channels_last)
+
+
+@torch.library.custom_op("mcgmil::bn_act_f32", mutates_args=())
+def bn_act_f32(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+               residual: Optional[torch.Tensor], eps: float, relu: bool
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+        return features.batchnorm_act_stats(_channels_last(x), f(weight), f(bias),
+                                            None if residual is None else _channels_last(residual), eps, relu)
+
+
+@bn_act_f32.register_fake
+def _bn_act_f32_fake(x, weight, bias, residual, eps, relu):
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    return y, x.new_empty((x.shape[1],), dtype=torch.float32), x.new_empty((x.shape[1],), dtype=torch.float32)
+
+
+@torch.library.custom_op("mcgmil::bn_act_f32_backward", mutates_args=())
+def bn_act_f32_backward(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                        mean: torch.Tensor, invstd: torch.Tensor, relu: bool, need_dx: bool, need_dres: bool,
+                        need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        dx, dres, dw, db = features.batchnorm_act_backward(
+            _channels_last(x), _channels_last(y) if relu else None, _channels_last(dy),
+            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
+            invstd.detach().contiguous(), relu, need_dx, need_dres, need_dw)
+    e = lambda t: x.new_empty((0,)) if t is None else t  # noqa: E731
+    return e(dx), e(dres), e(dw), e(db)
+
+
+@bn_act_f32_backward.register_fake
+def _bn_act_f32_backward_fake(x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
+    full = lambda need: torch.empty(x.shape, dtype=torch.float32, device=x.device,  # noqa: E731
+                                    memory_format=torch.channels_last) if need else x.new_empty((0,))
+    vec = lambda: x.new_empty((x.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+    return full(need_dx), full(need_dres and relu), vec(), vec()
+
+
+def _bn_setup_context(ctx, inputs, output):
+    x, weight, bias, residual, eps, relu = inputs
+    y, mean, invstd = output
+    ctx.relu, ctx.has_weight = relu, weight is not None
+    # y is needed for the ReLU mask only
+    ctx.save_for_backward(x, mean, invstd, *((weight,) if weight is not None else ()), *((y,) if relu else ()))
+    ctx.set_materialize_grads(False)
+
+
+def _bn_backward(ctx, dy, dmean, dinvstd):
+    # dmean / dinvstd: mean and invstd are by-products for the backward, not differentiable outputs
+    if dy is None:
+        return (None,) * 6
+    x, mean, invstd, *rest = ctx.saved_tensors
+    weight = rest.pop(0) if ctx.has_weight else None
+    y = rest.pop(0) if ctx.relu else x.new_empty((0,))
+    need = ctx.needs_input_grad
+    need_dx, need_dw, need_dres = need[0], need[1] or need[2], need[3]
+    dx, dres, dw, db = torch.ops.mcgmil.bn_act_f32_backward(x, y, dy, weight, mean, invstd, ctx.relu, need_dx,
+                                                            need_dres and ctx.relu, need_dw)
+    if need_dres and not ctx.relu:
+        dres = dy
+    return (dx if need_dx else None, dw if need[1] else None, db if need[2] else None,
+            dres if need_dres else None, None, None)
+
+
+bn_act_f32.register_autograd(_bn_backward, setup_context=_bn_setup_context)

@@ -18,8 +18,10 @@ What differs, by design:
     torch.ops.mcgmil.mcdo_forward, whose HIP backward (include/mcgmil_grad.h) draws the dropout
     masks again instead of storing them. enable_backbone_training() on top of it moves the
     backbone's block convolutions from the torch layers to the differentiable fp32 HIP op
-    (torch.ops.mcgmil.conv2d_f32; include/mcgmil_conv_grad.h is its native backward). Without the opt-in, forward() in train mode raises instead of
-    silently running elsewhere.
+    (torch.ops.mcgmil.conv2d_f32; include/mcgmil_conv_grad.h is its native backward), and with
+    norm=True the blocks' BatchNorm / residual add / ReLU to the fused HIP op
+    (torch.ops.mcgmil.bn_act_f32; include/mcgmil_bn_grad.h is its backward). Without the opt-in,
+    forward() in train mode raises instead of silently running elsewhere.
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
 """
@@ -98,6 +100,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_cache = None
         self._head_training = False
         self._backbone_training = False
+        self._norm_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -233,7 +236,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_training = bool(flag)
         return self
 
-    def enable_backbone_training(self, flag=True):
+    def enable_backbone_training(self, flag=True, *, norm=False):
         """With enable_head_training(): forward() in train mode runs the backbone's block
         convolutions (every features.conv32_trainable one: all but the 3-channel stem) through
         the differentiable op torch.ops.mcgmil.conv2d_f32 instead of the torch layer: the fp32
@@ -241,8 +244,15 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         (MCGMIL_CONV_GRAD=native: the HIP weight gradient and the forward kernel again as the
         stride-1 data gradient; default: aten.convolution_backward, which measured faster on
         every ResNet shape class). The stem, BatchNorm, ReLU, the pools and the
-        residual add stay on the torch layers. Off by default; returns self."""
+        residual add stay on the torch layers, unless norm=True: then every pool-free
+        features.bn_trainable BatchNorm of the blocks (fp32, batch statistics, no running-statistics
+        update pending), with the residual add and ReLU that follow it, runs through the
+        differentiable op torch.ops.mcgmil.bn_act_f32 as well: the fused HIP forward and the HIP
+        backward of include/mcgmil_bn_grad.h instead of torch's batch_norm / add / relu kernels and
+        their backward (timings in DESIGN.md §4). The stem (conv1 / bn1 / maxpool) stays on torch
+        either way. Off by default, norm off by default; returns self."""
         self._backbone_training = bool(flag)
+        self._norm_training = bool(flag) and bool(norm)
         return self
 
     def _live_head(self):
@@ -293,7 +303,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                 raise NotImplementedError("training is out of scope for the MI355X MCDO build; "
                                           "call forward() in eval mode or under torch.no_grad() "
                                           "(or opt in with enable_head_training())")
-            with features.native_conv_training(self._backbone_training):
+            with features.native_conv_training(self._backbone_training), \
+                    features.native_norm_training(self._norm_training):
                 H = self.extract_features(x)
             Y, A = self.forward_features(H, T=1, seed=seed)
             Y, A = Y[0], A[0]
