@@ -58,10 +58,14 @@ namespace {
 
 template <typename E, int PPW, int MAXC, bool ONE>
 int launch(const mcgmil::GateParams& gp, long long total_rows, hipStream_t s) {
-    auto* k = gp.clock ? &mcgmil::gate_fused_kernel<E, PPW, MAXC, ONE, true>   // MCGMIL_CLOCK_PROBE
-                       : &mcgmil::gate_fused_kernel<E, PPW, MAXC, ONE>;
-    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(k), "gate_fused_kernel LDS limit")) return rc;
     constexpr int cap = mcgmil::fused_cap<MAXC>();
+    // uniform bags of whole tiles: the affine kernel (no row tables); every other batch: row tables
+    const bool affine = mcgmil::fused_affine(gp.uniform_rows, cap);
+    auto* k = affine ? (gp.clock ? &mcgmil::gate_fused_kernel<E, PPW, MAXC, ONE, true>   // MCGMIL_CLOCK_PROBE
+                                 : &mcgmil::gate_fused_kernel<E, PPW, MAXC, ONE>)
+                     : (gp.clock ? &mcgmil::gate_fused_table_kernel<E, PPW, MAXC, ONE, true>
+                                 : &mcgmil::gate_fused_table_kernel<E, PPW, MAXC, ONE>);
+    if (int rc = raise_lds_limit(reinterpret_cast<const void*>(k), "gate_fused_kernel LDS limit")) return rc;
     if (gp.uniform_rows <= 0) {
         hipLaunchKernelGGL(mcgmil::plan_regions_kernel, dim3(1), dim3(1024), 0, s, gp.bag_off, gp.B,
                            gp.T, cap, const_cast<int32_t*>(gp.region_off));

@@ -196,6 +196,51 @@ __device__ __forceinline__ void load_head_vectors(const GateParams& p, int q0, i
     }
 }
 
+// A region of gate_fused_kernel: the t-groups [t0, t1) of one bag.
+struct Region {
+    int bag, t0, t1, Nb, ob;
+    int ntiles;                    // 128-row tiles
+    long long S, rows;
+};
+
+// What stays the same for every tile of a region, written to LDS once per workgroup by
+// gate_fused_kernel's affine launch (uniform bags of whole 128-row tiles): LDS costs the tile loop
+// no registers, and nothing here is recomputed or fetched from global memory per tile.
+constexpr int kFusedTiles = 32;    // tiles of a region whose logits stay in LDS (fused_cap / 128)
+constexpr int kFusedHv = 256;      // gate columns G * D of the 8-wave tile (16 pairs of 16)
+struct alignas(16) FusedConst {
+    Region rg;
+    uint32_t bagctr;               // the bag's Philox counter (bag_ids[bag] or bag_base + bag)
+    int pad0;
+    float ba[4];                   // attention bias per class
+    int cls[8];                    // per wave: the class of its gate pairs (idle waves: MAXC)
+    int pad1[8];
+    // tile i of the region's run order is sample t = x and instances y .. y + 127 of the bag (every
+    // row valid, H row ob + y + r); its logits start at row z of the region
+    int4 tile[kFusedTiles];
+    // separate heads: bv * kM2Log2e, bu * kMLog2e and wa of gate column 16 q + d of pair q
+    float hv[3][kFusedHv];
+};
+
+// The head vectors of the wave's pairs from FusedConst::hv (ds_read_b128, no division: pair q,
+// lane group lane >> 4 holds columns 16 q + 4 (lane >> 4) ..). MCGMIL_FUSED_HV_LDS=0 (A/B builds):
+// from global memory after the K loop, as the row-table launch.
+#ifndef MCGMIL_FUSED_HV_LDS
+#define MCGMIL_FUSED_HV_LDS 1
+#endif
+template <int PPW>
+__device__ __forceinline__ void load_head_vectors_lds(const FusedConst* fc, int P, int q0, int lane,
+                                                      HeadVec (&hv)[PPW]) {
+#pragma unroll
+    for (int jp = 0; jp < PPW; ++jp) {
+        const int q = q0 + jp < P ? q0 + jp : P - 1;
+        const int d = 16 * q + 4 * (lane >> 4);
+        hv[jp].bv = *reinterpret_cast<const f32x4*>(fc->hv[0] + d);
+        hv[jp].bu = *reinterpret_cast<const f32x4*>(fc->hv[1] + d);
+        hv[jp].wa = *reinterpret_cast<const f32x4*>(fc->hv[2] + d);
+    }
+}
+
 // Fold the gate pairs of one pass into per-lane partial scores. acc[rt][2j] / acc[rt][2j+1]
 // hold V / U pre-activations (before the dropout scale) of pair q0 + j for instance
 // rt*16 + (lane & 15) and d = 16*db + 4*(lane >> 4) + v (16x16 C layout, weights as A).
@@ -211,8 +256,11 @@ __device__ __forceinline__ void fold_pairs(const GateParams& p, const f32x4 (&ac
     for (int jp = 0; jp < PPW; ++jp) {
         const int q = q0 + jp;
         if (q >= p.P) break;
-        const int g = q / DB, db = q - g * DB;
-        const int d0 = db * 16 + 4 * (lane >> 4);
+        // gate column of the lane's first element: g * D + db * 16 + .. = 16 q + .. (D = 16 DB), so
+        // separate heads (wa row g = gate g) need no q / DB
+        const int col = 16 * q + 4 * (lane >> 4);
+        const int g = ONE_CLASS ? 0 : q / DB;
+        const int d0 = col - g * p.D;
         f32x4 bvv, buv;
         f32x4 coef[MAXC];
         if (ONE_CLASS && pre) {      // loaded before the K loop (load_head_vectors)
@@ -222,8 +270,8 @@ __device__ __forceinline__ void fold_pairs(const GateParams& p, const f32x4 (&ac
 #pragma unroll
             for (int c = 1; c < MAXC; ++c) coef[c] = f32x4{0.f, 0.f, 0.f, 0.f};
         } else {
-            bvv = *reinterpret_cast<const f32x4*>(p.bv + (size_t)g * p.D + d0);
-            buv = *reinterpret_cast<const f32x4*>(p.bu + (size_t)g * p.D + d0);
+            bvv = *reinterpret_cast<const f32x4*>(p.bv + col);
+            buv = *reinterpret_cast<const f32x4*>(p.bu + col);
             bvv *= kM2Log2e;
             buv *= kMLog2e;
 #pragma unroll
@@ -277,13 +325,16 @@ __host__ __device__ constexpr int red_floats() { return kGateWaves * MAXC * 4 * 
 // Output item of a thread: row wave*16 + (lane & 15), class lane >> 4 (C <= 4) -- the (row,
 // class) whose attention-dropout draw the pipelined kernel may already have made in its K
 // loop (have_keep, keep); otherwise it is drawn here.
-template <int BM, int MAXC, int ROWS = 16>
+// AFFINE (gate_fused_kernel's affine launch): no row table -- the rows are those of tile `tile` of
+// FusedConst, and the attention bias and the bag's Philox counter come from there as well.
+template <int BM, int MAXC, int ROWS = 16, bool AFFINE = false>
 __device__ __forceinline__ void finish_scores(const GateParams& p, long long R0,
                                               float (&part)[MAXC][BM / ROWS], f32x4 zacc,
                                               bool zwave, float* red, float* zred,
                                               const int* rinfo, int one_class, int waves_per_gate,
                                               bool have_keep, bool keep, float* lg_out,
-                                              float* z_out, long long obase) {
+                                              float* z_out, long long obase,
+                                              const FusedConst* fc = nullptr, int tile = 0) {
     constexpr int RT = BM / ROWS;
     constexpr int NG = 64 / ROWS;                  // lane groups per accumulator tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -306,8 +357,25 @@ __device__ __forceinline__ void finish_scores(const GateParams& p, long long R0,
     MCGMIL_STAMP(p, 6);
     const int r = wave * 16 + (lane & 15), c = lane >> 4;
     if (r >= BM || c >= p.C) return;
-    const int* ri = rinfo + kRowInfo * r;
-    if (ri[0] < 0) return;
+    int t, n, bag, Nb;
+    uint32_t bagc;
+    size_t orow;                                      // row of lg_out / z_out
+    float bias;
+    if constexpr (AFFINE) {
+        const int4 tl = fc->tile[tile];
+        t = tl.x, n = tl.y + r, bag = fc->rg.bag, Nb = fc->rg.Nb;
+        bagc = fc->bagctr;
+        orow = (size_t)(tl.z + r);
+        bias = fc->ba[c];
+    } else {
+        const int* ri = rinfo + kRowInfo * r;
+        if (ri[0] < 0) return;
+        t = ri[1], n = ri[2], bag = ri[3], Nb = ri[4];
+        bagc = (uint32_t)ri[5];
+        // row R0 + r of the flattened (bag, t, n) space -> lg_out / z_out row R0 + r - obase
+        orow = (size_t)(R0 + r - obase);
+        bias = p.ba[c];
+    }
     // waves holding class c: every wave (waves_per_gate = 0: shared gate) or, one class per
     // wave, the waves w with w / waves_per_gate == c (their other slots are never written)
     float s = 0.f;
@@ -318,17 +386,15 @@ __device__ __forceinline__ void finish_scores(const GateParams& p, long long R0,
 #pragma unroll
         for (int g = 0; g < NG; ++g) s += src[g * BM];
     }
-    s += p.ba[c];
-    const int t = ri[1], n = ri[2], bag = ri[3], Nb = ri[4];
+    s += bias;
     if (p.keep_att) {
         const size_t abase = (size_t)p.T * p.C * (size_t)p.bag_off[bag];
         keep = p.keep_att[abase + ((size_t)t * p.C + c) * Nb + n] != 0;
     } else if (!have_keep) {
-        keep = attention_keep(p.k0, p.k1, (uint32_t)ri[5], (uint32_t)(p.t_base + t), (uint32_t)c,
+        keep = attention_keep(p.k0, p.k1, bagc, (uint32_t)(p.t_base + t), (uint32_t)c,
                               (uint32_t)n, p.thr_a);
     }
-    // row R0 + r of the flattened (bag, t, n) space -> lg_out / z_out row R0 + r - obase
-    const size_t o = (size_t)(R0 + r - obase) * p.C + c;
+    const size_t o = orow * p.C + c;
     lg_out[o] = s * (keep ? p.sa : 0.f);
     z_out[o] = zred[c * BM + r] * p.sf;
 }
@@ -636,11 +702,15 @@ __device__ __forceinline__ void load_classifier_lds(__amdgpu_buffer_rsrc_t wrs, 
 // RTV < 8 (a short tile, gate_pipe_kernel's tail launch): row tiles RTV.. are padding -- no
 // MFMAs, no staging, no H loads and no epilogue for them; every row computes exactly as in a full
 // tile (same K order, same cross-wave sum), so the scores are bitwise the same.
+// AFFINE (gate_fused_kernel's affine launch): the rows are those of tile `tile` of FusedConst `fc`
+// instead of a row table (R0, rinfo and obase unused), and the head vectors, the wave's class, the
+// attention bias and the bag's Philox counter are read from `fc`.
 template <typename E, int PPW, int MAXC, bool REPLAY, bool ONE_CLASS, bool EARLY_HV = true,
-          bool ZL = false, bool ZLOAD = true, int RTV = kPipeBM / 16>
+          bool ZL = false, bool ZLOAD = true, int RTV = kPipeBM / 16, bool AFFINE = false>
 __device__ __forceinline__ void pipe_tile(const GateParams& p, long long R0, E* Xs, float* red,
                                           float* zred, const int* rinfo, float* lg_out,
-                                          float* z_out, long long obase, E* zw = nullptr) {
+                                          float* z_out, long long obase, E* zw = nullptr,
+                                          const FusedConst* fc = nullptr, int tile = 0) {
     constexpr int BM = kPipeBM;
     constexpr int RT = BM / 16;                     // 8 row tiles = 8 waves
     constexpr int NJ = 2 * PPW;
@@ -650,12 +720,23 @@ __device__ __forceinline__ void pipe_tile(const GateParams& p, long long R0, E* 
 
     // staging item of this thread: row wave*16 + (lane & 15), 8-chunk kq = lane >> 4 of
     // every K step; it lands at lane slot `lane` of row tile `wave` (= element tid*8)
-    const int* ri = rinfo + kRowInfo * (wave * 16 + (lane & 15));
-    const int hrow = ri[0];
-    const bool valid = hrow >= 0;
+    int hrow;
+    uint32_t cn, ct, cb;
+    if constexpr (AFFINE) {
+        static_assert(!REPLAY, "the affine rows have no replay masks");
+        const int4 tl = fc->tile[tile];
+        cn = (uint32_t)(tl.y + wave * 16 + (lane & 15));
+        hrow = fc->rg.ob + (int)cn;
+        ct = (uint32_t)(p.t_base + tl.x);
+        cb = fc->bagctr;
+    } else {
+        const int* ri = rinfo + kRowInfo * (wave * 16 + (lane & 15));
+        hrow = ri[0];
+        cn = (uint32_t)ri[2], ct = (uint32_t)(p.t_base + ri[1]), cb = (uint32_t)ri[5];
+    }
+    const bool valid = AFFINE || hrow >= 0;
     const int kq = lane >> 4;
     const E* hsrc = reinterpret_cast<const E*>(p.H) + (size_t)(valid ? hrow : 0) * p.ldh + kq * 8;
-    const uint32_t cn = (uint32_t)ri[2], ct = (uint32_t)(p.t_base + ri[1]), cb = (uint32_t)ri[5];
     // replay row (row 0 for padding rows, whose bits are masked off by vmask)
     const uint8_t* kfe = REPLAY ? p.keep_feat + (size_t)(valid ? R0 + wave * 16 + (lane & 15) : 0) *
                                                     (p.L >> 3) + kq
@@ -819,12 +900,19 @@ __device__ __forceinline__ void pipe_tile(const GateParams& p, long long R0, E* 
     for (int c = 0; c < MAXC; ++c)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) part[c][rt] = 0.f;
-    fold_pairs<RT, PPW, MAXC, ONE_CLASS, RTV>(p, acc, q0, lane, part, kEarlyHV ? hvec : nullptr);
+    // affine launch, separate heads: both pairs' head vectors from LDS, issued here, where the
+    // weight and fragment registers of the K loop are dead
+    constexpr bool kLdsHV = MCGMIL_FUSED_HV_LDS && AFFINE && ONE_CLASS && !kEarlyHV;
+    if constexpr (kLdsHV) load_head_vectors_lds<PPW>(fc, p.P, q0, lane, hvec);
+    fold_pairs<RT, PPW, MAXC, ONE_CLASS, RTV>(p, acc, q0, lane, part, kEarlyHV || kLdsHV ? hvec : nullptr);
     MCGMIL_STAMP(p, 4);
     // ONE_CLASS: the wave's pairs all belong to gate q0 / (D/16) (idle waves: class >= C)
-    const int one_class = ONE_CLASS ? (q0 < p.P ? q0 / (p.D >> 4) : MAXC) : -1;
-    finish_scores<BM, MAXC>(p, R0, part, zacc, true, red, zred, rinfo, one_class,
-                            ONE_CLASS ? (p.D >> 4) / PPW : 0, false, true, lg_out, z_out, obase);
+    int one_class = -1;
+    if constexpr (ONE_CLASS && AFFINE) one_class = __builtin_amdgcn_readfirstlane(fc->cls[wave]);
+    else if constexpr (ONE_CLASS) one_class = q0 < p.P ? q0 / (p.D >> 4) : MAXC;
+    finish_scores<BM, MAXC, 16, AFFINE>(p, R0, part, zacc, true, red, zred, rinfo, one_class,
+                                        ONE_CLASS ? (p.D >> 4) / PPW : 0, false, true, lg_out, z_out,
+                                        obase, fc, tile);
     MCGMIL_STAMP(p, 7);
 }
 
@@ -885,7 +973,9 @@ __global__ __launch_bounds__(kGateThreads) void gate_pipe_kernel(const GateParam
 // then runs softmax_group on each t-group, two at a time (threads 0-255 and 256-511): A and
 // Y are written once and no logit leaves the CU. Bags of more than fused_cap instances keep
 // one t-group per region and go through the global workspace instead (the workgroup re-reads
-// its own writes).
+// its own writes). Two kernels share the body (fused_region): gate_fused_kernel, the affine
+// launch for uniform bags of whole tiles (no row tables; region constants and head vectors in
+// LDS, FusedConst), and gate_fused_table_kernel with a row table per tile for every other batch.
 // ---------------------------------------------------------------------------------------
 #ifndef MCGMIL_FUSED_XCD
 #define MCGMIL_FUSED_XCD 1         // 1: regions of bag b on XCD b % 8 (uniform bags, B % 8 == 0)
@@ -908,7 +998,15 @@ template <typename E, int MAXC>
 __host__ __device__ constexpr size_t fused_lds_bytes() {
     return pipe_lds_bytes<E, MAXC>() + (size_t)kRowInfo * kPipeBM * 4   // second row table
            + (size_t)2 * fused_cap<MAXC>() * MAXC * 4                   // logits + z of a region
-           + (size_t)2 * 16 * 4 + 64;                                   // softmax partials, region
+           + (size_t)2 * 16 * 4 + sizeof(FusedConst);                   // softmax partials, region constants
+}
+static_assert(kFusedTiles * kPipeBM >= MCGMIL_FUSED_CAP, "FusedConst::tile holds a whole region");
+
+// The affine launch: every bag has N rows, a multiple of the 128-row tile, and a region's logits
+// fit in LDS. Then every region is whole t-groups of whole tiles, every row of every tile is
+// valid, and a tile is one sample t and 128 consecutive instances (the host picks the kernel).
+__host__ __device__ inline bool fused_affine(int uniform_rows, int cap) {
+    return uniform_rows > 0 && uniform_rows % kPipeBM == 0 && uniform_rows <= cap;
 }
 
 // bf16: the classifier tile's weight fragments of every K step stay in LDS for the workgroup's
@@ -930,12 +1028,6 @@ __host__ __device__ inline int region_t_groups(int Nb, int T, int cap) {
     const int ts = cap / Nb;
     return ts < T ? ts : T;
 }
-
-struct Region {
-    int bag, t0, t1, Nb, ob;
-    int ntiles;                    // 128-row tiles
-    long long S, rows;
-};
 
 // Tile i of a region's run order. MCGMIL_FUSED_NMAJOR: when the region is G > 1 t-groups of
 // whole tiles, instance-block major -- tile i reads the same 128 H rows as tile i-1 for G-1 of
@@ -1018,8 +1110,43 @@ __device__ __forceinline__ void fill_row_table_region(const GateParams& p, const
 }
 
 
-template <typename E, int PPW, int MAXC, bool ONE_CLASS, bool PROBE = false>
-__global__ __launch_bounds__(kGateThreads) void gate_fused_kernel(const GateParams p) {
+// FusedConst of a region of the affine launch, by the whole workgroup (visible after the caller's
+// barrier). Exact small-integer divisions as counting loops: once per workgroup, and no division
+// chain in the kernel.
+template <int PPW, int MAXC, bool ONE_CLASS>
+__device__ __forceinline__ void fill_fused_const(const GateParams& p, const Region& rg, FusedConst* fc) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        fc->rg = rg;
+        fc->bagctr = p.bag_ids ? p.bag_ids[rg.bag] : p.bag_base + (uint32_t)rg.bag;
+    }
+    if (tid < MAXC) fc->ba[tid] = tid < p.C ? p.ba[tid] : 0.f;
+    if (tid < kGateWaves) {        // class of wave tid's pairs: (tid * PPW) / (D / 16)
+        const int q0 = tid * PPW, DB = p.D >> 4;
+        int g = 0;
+        while ((g + 1) * DB <= q0) ++g;
+        fc->cls[tid] = ONE_CLASS && q0 < p.P ? g : MAXC;
+    }
+    if (tid < rg.ntiles && tid < kFusedTiles) {   // tile tid of region_tile's order
+        const int G = rg.t1 - rg.t0, nbt = rg.Nb / kPipeBM;
+        const int dv = MCGMIL_FUSED_NMAJOR ? G : nbt;
+        int qt = 0;
+        while ((qt + 1) * dv <= tid) ++qt;
+        const int rem = tid - qt * dv;
+        const int tg = MCGMIL_FUSED_NMAJOR ? rem : qt, nb = MCGMIL_FUSED_NMAJOR ? qt : rem;
+        fc->tile[tid] = make_int4(rg.t0 + tg, nb * kPipeBM, tg * rg.Nb + nb * kPipeBM, 0);
+    }
+    if (ONE_CLASS && tid < 16 * p.P && tid < kFusedHv) {
+        fc->hv[0][tid] = p.bv[tid] * kM2Log2e;
+        fc->hv[1][tid] = p.bu[tid] * kMLog2e;
+        fc->hv[2][tid] = p.wa[tid];       // separate heads: wa[g][d] of gate g = class g
+    }
+}
+
+// The body of the two fused kernels. AFFINE: see fused_affine and FusedConst; otherwise the
+// rows of every tile come from a row table (ragged bags, bags of partial tiles or above fused_cap).
+template <typename E, int PPW, int MAXC, bool ONE_CLASS, bool PROBE, bool AFFINE>
+__device__ __forceinline__ void fused_region(const GateParams& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BM = kPipeBM;
     constexpr int CAP = fused_cap<MAXC>();
@@ -1030,6 +1157,7 @@ __global__ __launch_bounds__(kGateThreads) void gate_fused_kernel(const GatePara
     float* slg = reinterpret_cast<float*>(rinfo + 2 * kRowInfo * BM);    // [CAP][C]
     float* szz = slg + CAP * MAXC;                                        // [CAP][C]
     float* sred = szz + CAP * MAXC;                                       // [2][16]
+    FusedConst* fc = reinterpret_cast<FusedConst*>(sred + 32);
 
 #if MCGMIL_DIAG & 64   // diagnostic (timing only): gate_pipe_kernel's work in this kernel's frame
     {
@@ -1045,42 +1173,52 @@ __global__ __launch_bounds__(kGateThreads) void gate_fused_kernel(const GatePara
     if constexpr (PROBE) clock_probe(p, 0);
     const int ntiles = (int)((rg.rows + BM - 1) / BM);
     // The tile loop keeps almost nothing in registers across tiles: the region sits in LDS and
-    // the parameters are re-read from the kernarg segment in every tile, both through pointers
-    // the compiler cannot see through. Hoisted out of the loop, the ~40 scalar parameters and
+    // the parameters are re-read from the kernarg segment in every tile (through a pointer the
+    // compiler cannot see through). Hoisted out of the loop, the ~40 scalar parameters and
     // the region stay live across it, and the SGPR spills (into VGPR lanes) push the tile over
     // 256 VGPRs.
-    Region* srg = reinterpret_cast<Region*>(sred + 32);
-    if (threadIdx.x == 0) *srg = rg;
-    __syncthreads();                                 // *srg is read by every wave from tile 0 on
+    Region* srg = &fc->rg;
+    if constexpr (AFFINE) fill_fused_const<PPW, MAXC, ONE_CLASS>(p, rg, fc);
+    else if (threadIdx.x == 0) *srg = rg;
+    __syncthreads();                                 // *fc is read by every wave from tile 0 on
     E* zw = reinterpret_cast<E*>(smem + fused_lds_bytes<E, MAXC>());
     if constexpr (fused_zl<E>())
         load_classifier_lds<E>(make_rsrc(p.Wp, p.wp_bytes), (uint32_t)(2 * p.P) * (uint32_t)(p.L >> 5) * 512u *
                                    (uint32_t)sizeof(E), p.L >> 5, zw);   // visible after tile 0's first barrier
     for (int i = 0; i < ntiles; ++i) {
-        Region* qr = srg;
-        asm volatile("" : "+v"(qr));
         const GateParams pt = reload_kernarg_params(p);
-        // two row tables: tile i fills one while tile i-1's scoring may still read the other
-        int* ri = rinfo + (i & 1) * kRowInfo * BM;
-        MCGMIL_STAMP(pt, 0);
-        {
+        if constexpr (AFFINE) {
+            // no row table and no barrier for one: tile i-1's scoring reads only red / zred, which
+            // tile i first writes after its K loop's barriers
+            MCGMIL_STAMP(pt, 0);
+            MCGMIL_STAMP(pt, 1);
+            pipe_tile<E, PPW, MAXC, false, ONE_CLASS, MCGMIL_FUSED_EARLY_HV, fused_zl<E>(), false, BM / 16, true>(
+                pt, 0, Xs, red, zred, nullptr, slg, szz, 0, zw, fc, i);
+        } else {
+            Region* qr = srg;
+            asm volatile("" : "+v"(qr));
+            // two row tables: tile i fills one while tile i-1's scoring may still read the other
+            int* ri = rinfo + (i & 1) * kRowInfo * BM;
+            MCGMIL_STAMP(pt, 0);
+            {
+                const Region r = *qr;
+                fill_row_table_region<BM>(pt, r, r.S + (long long)region_tile(r, i) * BM, ri);
+            }
+            __syncthreads();
+            MCGMIL_STAMP(pt, 1);
             const Region r = *qr;
-            fill_row_table_region<BM>(pt, r, r.S + (long long)region_tile(r, i) * BM, ri);
+            const bool lds = r.Nb <= CAP;
+            pipe_tile<E, PPW, MAXC, false, ONE_CLASS, MCGMIL_FUSED_EARLY_HV, fused_zl<E>(), false>(
+                pt, r.S + (long long)region_tile(r, i) * BM, Xs, red, zred, ri, lds ? slg : pt.logits,
+                lds ? szz : pt.zz, lds ? r.S : 0, zw);
         }
-        __syncthreads();
-        MCGMIL_STAMP(pt, 1);
-        const Region r = *qr;
-        const bool lds = r.Nb <= CAP;
-        pipe_tile<E, PPW, MAXC, false, ONE_CLASS, MCGMIL_FUSED_EARLY_HV, fused_zl<E>(), false>(
-            pt, r.S + (long long)region_tile(r, i) * BM, Xs, red, zred, ri, lds ? slg : pt.logits,
-            lds ? szz : pt.zz, lds ? r.S : 0, zw);
     }
     __syncthreads();
 #if MCGMIL_DIAG & 32   // ablation (timing only, no A/Y): no softmax phase
     if (ntiles >= 0) return;
 #endif
     rg = *srg;
-    const bool in_lds = rg.Nb <= CAP;
+    const bool in_lds = AFFINE || rg.Nb <= CAP;
 
     // softmax + pooling per t-group (model.py:305-316), two groups at a time
     const int G = rg.t1 - rg.t0;
@@ -1096,6 +1234,18 @@ __global__ __launch_bounds__(kGateThreads) void gate_fused_kernel(const GatePara
         softmax_group(ltid, act, rg.Nb, p.C, lgj, zzj, Ao, Yo, sred + half * 16);
     }
     if constexpr (PROBE) clock_probe(p, 1);
+}
+
+// The affine launch (the host takes it whenever fused_affine holds: the bench's shape) ...
+template <typename E, int PPW, int MAXC, bool ONE_CLASS, bool PROBE = false>
+__global__ __launch_bounds__(kGateThreads) void gate_fused_kernel(const GateParams p) {
+    fused_region<E, PPW, MAXC, ONE_CLASS, PROBE, true>(p);
+}
+
+// ... and the row-table launch for every other batch.
+template <typename E, int PPW, int MAXC, bool ONE_CLASS, bool PROBE = false>
+__global__ __launch_bounds__(kGateThreads) void gate_fused_table_kernel(const GateParams p) {
+    fused_region<E, PPW, MAXC, ONE_CLASS, PROBE, false>(p);
 }
 
 // ---------------------------------------------------------------------------------------
