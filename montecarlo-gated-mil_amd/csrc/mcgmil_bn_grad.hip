@@ -289,6 +289,18 @@ void launch_apply(const mcgmil_bn_grad_args* a, const float* coef, hipStream_t s
 
 }  // namespace
 
+namespace mcgmil_detail {
+
+// bn_grad_finalize_kernel for another backward with the same [parts][2][C] partials and [3][C]
+// coefficients (mcgmil_pool_grad.hip); the caller checks hipGetLastError().
+void bn_grad_finalize(const float* part, long long parts, long long rows, int C, const float* gamma,
+                      const float* invstd, float* coef, float* dgamma, float* dbeta, hipStream_t s) {
+    hipLaunchKernelGGL(bn_grad_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kThreads), 0, s, part, parts,
+                       rows, C, gamma, invstd, coef, dgamma, dbeta);
+}
+
+}  // namespace mcgmil_detail
+
 extern "C" {
 
 size_t mcgmil_bn_grad_args_size(void) { return sizeof(mcgmil_bn_grad_args); }

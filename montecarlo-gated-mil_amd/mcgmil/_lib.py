@@ -57,6 +57,9 @@ CONV_GRAD_EXPORTED = ("mcgmil_conv_grad_args_size", "mcgmil_conv_wgrad_workspace
 # include/mcgmil_bn_grad.h (the fused BatchNorm/add/ReLU's backward; additive as well)
 BN_GRAD_EXPORTED = ("mcgmil_bn_grad_args_size", "mcgmil_bn_grad_workspace_size",
                     "mcgmil_batchnorm_act_backward")
+# include/mcgmil_pool_grad.h (the stem's BatchNorm/ReLU/max-pool training op; additive as well)
+POOL_GRAD_EXPORTED = ("mcgmil_batchnorm_pool_train", "mcgmil_bn_pool_grad_args_size",
+                      "mcgmil_bn_pool_grad_workspace_size", "mcgmil_batchnorm_pool_backward")
 
 _vp = ctypes.c_void_p
 
@@ -151,6 +154,23 @@ class BnGradArgs(ctypes.Structure):
 
 
 BN_GRAD_PART_ELEMS = 32768         # MCGMIL_BN_GRAD_PART_ELEMS
+
+
+class BnPoolGradArgs(ctypes.Structure):
+    """Mirror of struct mcgmil_bn_pool_grad_args (include/mcgmil_pool_grad.h)."""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+        ("channels", ctypes.c_int32), ("pool_kernel", ctypes.c_int32), ("pool_stride", ctypes.c_int32),
+        ("pool_pad", ctypes.c_int32), ("pooled_height", ctypes.c_int32), ("pooled_width", ctypes.c_int32),
+        ("reserved32", ctypes.c_int32),
+        ("z", _vp), ("argmax", _vp), ("dy", _vp), ("gamma", _vp), ("mean", _vp), ("invstd", _vp),
+        ("dz", _vp), ("dgamma", _vp), ("dbeta", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int64),
+    ]
+
+
+BN_POOL_GRAD_PART_ELEMS = 32768    # MCGMIL_BN_POOL_GRAD_PART_ELEMS
+POOL_ARGMAX_NONE = 255             # MCGMIL_POOL_ARGMAX_NONE
 
 
 class StemArgs(ctypes.Structure):
@@ -307,6 +327,17 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_bn_grad_args_size() != ctypes.sizeof(BnGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_grad_args)={L.mcgmil_bn_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(BnGradArgs)} bytes")
+    ppg = ctypes.POINTER(BnPoolGradArgs)
+    L.mcgmil_batchnorm_pool_train.argtypes = [pb, _vp, _vp]
+    L.mcgmil_batchnorm_pool_train.restype = ctypes.c_int
+    L.mcgmil_bn_pool_grad_args_size.restype = ctypes.c_size_t
+    L.mcgmil_bn_pool_grad_workspace_size.argtypes = [ppg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_bn_pool_grad_workspace_size.restype = ctypes.c_int
+    L.mcgmil_batchnorm_pool_backward.argtypes = [ppg, _vp]
+    L.mcgmil_batchnorm_pool_backward.restype = ctypes.c_int
+    if L.mcgmil_bn_pool_grad_args_size() != ctypes.sizeof(BnPoolGradArgs):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_pool_grad_args)={L.mcgmil_bn_pool_grad_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(BnPoolGradArgs)} bytes")
     ps = ctypes.POINTER(StemArgs)
     L.mcgmil_stem_args_size.restype = ctypes.c_size_t
     for name in ("mcgmil_stem_packed_size", "mcgmil_stem_workspace_size"):

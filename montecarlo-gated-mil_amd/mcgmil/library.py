@@ -15,6 +15,10 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.bn_act_f32_backward(x, y, dy, weight?, mean, invstd, relu, need_dx, need_dres,
                                          need_dw) -> (dx, dres, dweight, dbias)
 
+    torch.ops.mcgmil.bn_pool_f32(z, weight?, bias?, eps, relu, k, stride, pad) -> (y, mean, invstd, argmax)
+    torch.ops.mcgmil.bn_pool_f32_backward(z, argmax, dy, weight?, mean, invstd, k, stride, pad, need_dz,
+                                          need_dw) -> (dz, dweight, dbias)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -36,6 +40,15 @@ backward: gradients flowing into them are ignored (they are not differentiable o
 ReLU the residual's gradient is dy itself: bn_act_f32_backward then returns an empty dres and the
 formula passes dy on.
 
+bn_pool_f32 is the stem's max_pool2d(relu?(batch_norm(z)), k, stride, pad) on the batch statistics
+of z (fp32, channels-last; k in {2, 3}, 1 <= stride <= k, pad <= k / 2): the fused forward
+features.batchnorm_pool_stats, which also returns mean, 1 / sqrt(var + eps) and one uint8 per
+pooled element that names the window's winning tap (255: the ReLU zeroes that gradient). It is
+differentiable in z, weight and bias; its formula saves only z, argmax, mean, invstd and weight
+(neither the activation nor y, nor int64 indices) and calls bn_pool_f32_backward
+(features.batchnorm_pool_backward, include/mcgmil_pool_grad.h), which has no formula itself.
+Gradients flowing into mean, invstd and argmax are ignored.
+
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
@@ -49,7 +62,7 @@ import torch
 from . import features, ops
 
 __all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
-           "bn_act_f32", "bn_act_f32_backward"]
+           "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -274,3 +287,71 @@ def _bn_backward(ctx, dy, dmean, dinvstd):
 
 
 bn_act_f32.register_autograd(_bn_backward, setup_context=_bn_setup_context)
+
+
+@torch.library.custom_op("mcgmil::bn_pool_f32", mutates_args=())
+def bn_pool_f32(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+                relu: bool, k: int, stride: int, pad: int
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+        return features.batchnorm_pool_stats(_channels_last(z), f(weight), f(bias), eps, relu, k, stride, pad)
+
+
+def _pooled_shape(z, k, stride, pad):
+    return (z.shape[0], z.shape[1], (z.shape[2] + 2 * pad - k) // stride + 1, (z.shape[3] + 2 * pad - k) // stride + 1)
+
+
+@bn_pool_f32.register_fake
+def _bn_pool_f32_fake(z, weight, bias, eps, relu, k, stride, pad):
+    shape = _pooled_shape(z, k, stride, pad)
+    y = torch.empty(shape, dtype=torch.float32, device=z.device, memory_format=torch.channels_last)
+    argmax = torch.empty(shape, dtype=torch.uint8, device=z.device, memory_format=torch.channels_last)
+    return (y, z.new_empty((z.shape[1],), dtype=torch.float32), z.new_empty((z.shape[1],), dtype=torch.float32),
+            argmax)
+
+
+@torch.library.custom_op("mcgmil::bn_pool_f32_backward", mutates_args=())
+def bn_pool_f32_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                         mean: torch.Tensor, invstd: torch.Tensor, k: int, stride: int, pad: int, need_dz: bool,
+                         need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        dz, dw, db = features.batchnorm_pool_backward(
+            _channels_last(z), _channels_last(argmax), _channels_last(dy),
+            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
+            invstd.detach().contiguous(), k, stride, pad, need_dz, need_dw)
+    e = lambda t: z.new_empty((0,)) if t is None else t  # noqa: E731
+    return e(dz), e(dw), e(db)
+
+
+@bn_pool_f32_backward.register_fake
+def _bn_pool_f32_backward_fake(z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
+    dz = torch.empty(z.shape, dtype=torch.float32, device=z.device, memory_format=torch.channels_last) \
+        if need_dz else z.new_empty((0,))
+    vec = lambda: z.new_empty((z.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+    return dz, vec(), vec()
+
+
+def _bn_pool_setup_context(ctx, inputs, output):
+    z, weight, bias, eps, relu, k, stride, pad = inputs
+    y, mean, invstd, argmax = output
+    ctx.geometry, ctx.has_weight = (k, stride, pad), weight is not None
+    # neither y nor the activation: the codes say where each pooled gradient goes
+    ctx.save_for_backward(z, argmax, mean, invstd, *((weight,) if weight is not None else ()))
+    ctx.set_materialize_grads(False)
+
+
+def _bn_pool_backward(ctx, dy, dmean, dinvstd, dargmax):
+    # dmean / dinvstd / dargmax: by-products for the backward, not differentiable outputs
+    if dy is None:
+        return (None,) * 8
+    z, argmax, mean, invstd, *rest = ctx.saved_tensors
+    weight = rest[0] if ctx.has_weight else None
+    need = ctx.needs_input_grad
+    need_dz, need_dw = need[0], need[1] or need[2]
+    dz, dw, db = torch.ops.mcgmil.bn_pool_f32_backward(z, argmax, dy, weight, mean, invstd, *ctx.geometry,
+                                                       need_dz, need_dw)
+    return (dz if need_dz else None, dw if need[1] else None, db if need[2] else None) + (None,) * 5
+
+
+bn_pool_f32.register_autograd(_bn_pool_backward, setup_context=_bn_pool_setup_context)

@@ -20,8 +20,10 @@ What differs, by design:
     backbone's block convolutions from the torch layers to the differentiable fp32 HIP op
     (torch.ops.mcgmil.conv2d_f32; include/mcgmil_conv_grad.h is its native backward), and with
     norm=True the blocks' BatchNorm / residual add / ReLU to the fused HIP op
-    (torch.ops.mcgmil.bn_act_f32; include/mcgmil_bn_grad.h is its backward). Without the opt-in,
-    forward() in train mode raises instead of silently running elsewhere.
+    (torch.ops.mcgmil.bn_act_f32; include/mcgmil_bn_grad.h is its backward), and with stem=True
+    the stem's BatchNorm / ReLU / max-pool to torch.ops.mcgmil.bn_pool_f32
+    (include/mcgmil_pool_grad.h). Without the opt-in, forward() in train mode raises instead of
+    silently running elsewhere.
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
 """
@@ -101,6 +103,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_training = False
         self._backbone_training = False
         self._norm_training = False
+        self._stem_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -236,7 +239,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_training = bool(flag)
         return self
 
-    def enable_backbone_training(self, flag=True, *, norm=False):
+    def enable_backbone_training(self, flag=True, *, norm=False, stem=False):
         """With enable_head_training(): forward() in train mode runs the backbone's block
         convolutions (every features.conv32_trainable one: all but the 3-channel stem) through
         the differentiable op torch.ops.mcgmil.conv2d_f32 instead of the torch layer: the fp32
@@ -249,10 +252,18 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         update pending), with the residual add and ReLU that follow it, runs through the
         differentiable op torch.ops.mcgmil.bn_act_f32 as well: the fused HIP forward and the HIP
         backward of include/mcgmil_bn_grad.h instead of torch's batch_norm / add / relu kernels and
-        their backward (timings in DESIGN.md §4). The stem (conv1 / bn1 / maxpool) stays on torch
-        either way. Off by default, norm off by default; returns self."""
+        their backward (timings in DESIGN.md §4). The stem (conv1 / bn1 / relu / maxpool) stays on
+        torch, unless stem=True: then the stem's BatchNorm / ReLU / max-pool, when
+        features.bn_pool_trainable, run through the differentiable op torch.ops.mcgmil.bn_pool_f32:
+        the fused HIP forward, which keeps one byte per pooled element instead of the ReLU output
+        and the pool's int64 indices, and the HIP backward of include/mcgmil_pool_grad.h (timings
+        in DESIGN.md §4). stem does not depend on norm; it only needs the flag itself. The 7x7
+        convolution's forward and backward stay on torch either way, because
+        features.conv32_trainable refuses 3 input channels. Off by default, norm and stem off by
+        default; returns self."""
         self._backbone_training = bool(flag)
         self._norm_training = bool(flag) and bool(norm)
+        self._stem_training = bool(flag) and bool(stem)
         return self
 
     def _live_head(self):
@@ -304,7 +315,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                                           "call forward() in eval mode or under torch.no_grad() "
                                           "(or opt in with enable_head_training())")
             with features.native_conv_training(self._backbone_training), \
-                    features.native_norm_training(self._norm_training):
+                    features.native_norm_training(self._norm_training), \
+                    features.native_stem_training(self._stem_training):
                 H = self.extract_features(x)
             Y, A = self.forward_features(H, T=1, seed=seed)
             Y, A = Y[0], A[0]
