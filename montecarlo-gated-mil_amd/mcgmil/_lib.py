@@ -60,6 +60,9 @@ BN_GRAD_EXPORTED = ("mcgmil_bn_grad_args_size", "mcgmil_bn_grad_workspace_size",
 # include/mcgmil_pool_grad.h (the stem's BatchNorm/ReLU/max-pool training op; additive as well)
 POOL_GRAD_EXPORTED = ("mcgmil_batchnorm_pool_train", "mcgmil_bn_pool_grad_args_size",
                       "mcgmil_bn_pool_grad_workspace_size", "mcgmil_batchnorm_pool_backward")
+# include/mcgmil_stem_grad.h (the stem convolution's weight gradient, on mcgmil_conv_grad_args;
+# additive as well)
+STEM_GRAD_EXPORTED = ("mcgmil_stem_wgrad_workspace_size_f32", "mcgmil_stem_wgrad_f32")
 
 _vp = ctypes.c_void_p
 
@@ -315,6 +318,10 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     L.mcgmil_conv_wgrad_workspace_size_f32.restype = ctypes.c_int
     L.mcgmil_conv2d_wgrad_f32.argtypes = [pcg, _vp]
     L.mcgmil_conv2d_wgrad_f32.restype = ctypes.c_int
+    L.mcgmil_stem_wgrad_workspace_size_f32.argtypes = [pcg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_stem_wgrad_workspace_size_f32.restype = ctypes.c_int
+    L.mcgmil_stem_wgrad_f32.argtypes = [pcg, _vp]
+    L.mcgmil_stem_wgrad_f32.restype = ctypes.c_int
     if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")

@@ -42,6 +42,10 @@ Inside `native_stem_training()` (enable_backbone_training(stem=True)) `bn_act` s
 torch.ops.mcgmil.bn_pool_f32: `batchnorm_pool_stats` is its forward (mcgmil_batchnorm_pool_train:
 batchnorm_act's pooled output bit for bit, plus one byte per pooled element that names the
 window's winning tap), `batchnorm_pool_backward` its HIP backward (include/mcgmil_pool_grad.h).
+Inside `native_stem_conv_training()` (enable_backbone_training(stem_conv=True)) `run_conv` sends a
+`stem_conv_trainable` convolution (1..4 input channels: the 7x7 stem) that autograd tracks to
+torch.ops.mcgmil.stem_conv_f32: `conv2d_f32` in its gather mode is the forward,
+`conv2d_f32_stem_wgrad` the HIP weight gradient (include/mcgmil_stem_grad.h).
 """
 import contextlib
 import ctypes
@@ -493,6 +497,105 @@ def conv2d_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     return torch.ops.mcgmil.conv2d_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
 
 
+# ---------------------------------------------------------------- fp32 stem convolution backward
+_native_stem_conv_training = False
+
+
+@contextlib.contextmanager
+def native_stem_conv_training(flag: bool = True):
+    """Inside this context `run_conv` sends a `stem_conv_trainable` convolution that autograd
+    tracks (the 7x7 stem, 3 input channels) to the differentiable op torch.ops.mcgmil.stem_conv_f32:
+    the gather-mode forward kernel and the HIP weight gradient of include/mcgmil_stem_grad.h. Off
+    outside it: the opt-in of MultiHeadGatedAttentionMIL.enable_backbone_training(stem_conv=True)."""
+    global _native_stem_conv_training
+    before, _native_stem_conv_training = _native_stem_conv_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_stem_conv_training = before
+
+
+def stem_conv_untrainable_reason(conv: nn.Conv2d, x: torch.Tensor) -> Optional[str]:
+    """Why conv on x is not a convolution whose forward AND weight gradient run on the fp32 HIP
+    kernels for few input channels (include/mcgmil_stem_grad.h), or None when it is. The conditions
+    are those of conv32_trainable with 1 <= in_channels <= 4 in place of in_channels % 16 == 0."""
+    if not conv32_enabled():
+        return "the native fp32 convolutions are switched off (MCGMIL_NATIVE_CONV32 / MCGMIL_NATIVE_CONV)"
+    if not isinstance(conv, nn.Conv2d):
+        return "not an nn.Conv2d"
+    if not (x.is_cuda and x.dim() == 4):
+        return "the activation is not a 4-d CUDA tensor"
+    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32:
+        return "the activation and the weight must be fp32"
+    if torch.is_autocast_enabled("cuda"):
+        return "autocast is enabled"
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return "only a bias-free groups=1 zero-padded convolution"
+    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
+            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
+        return "dilation 1, a square stride of 1 or 2 and a square integer padding"
+    kh, kw = conv.kernel_size
+    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
+        return "kernel 1..7 per axis and pad < min(kh, kw)"
+    if not 1 <= conv.in_channels <= 4:
+        return "in_channels must be in 1..4"
+    if conv.out_channels % 64 or conv.out_channels > 4096:
+        return "out_channels must be a multiple of 64 (at most 4096)"
+    if x.shape[1] != conv.in_channels:
+        return "the activation's channels are not the convolution's in_channels"
+    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
+        return "the activation must be non-empty and channels-last"
+    s, p = _square(conv.stride), _square(conv.padding)
+    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
+    if not (oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256):
+        return "batch * OH * OW must be in 1 .. 2^31 - 257"
+    return None
+
+
+def stem_conv_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """stem_conv_untrainable_reason(conv, x) is None. Says nothing about autograd."""
+    return stem_conv_untrainable_reason(conv, x) is None
+
+
+def conv2d_f32_stem_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
+    """dW [out, in, kh, kw] fp32 of conv(x) given dY for a `stem_conv_trainable` convolution, on the
+    HIP kernel mcgmil_stem_wgrad_f32: the sibling of conv2d_f32_wgrad for 1..4 input channels.
+    chunk_pixels as there; the result does not depend on it, bitwise."""
+    reason = stem_conv_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_f32_stem_wgrad: {reason} (see stem_conv_trainable)")
+    L = _lib.load()
+    g = _lib.ConvGradArgs()
+    a = g.fwd
+    a.batch, _, a.height, a.width = x.shape
+    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
+    a.kernel_h, a.kernel_w = conv.kernel_size
+    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
+    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
+    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
+    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.float32 or dy.device != x.device:
+        raise ValueError(f"dy must be fp32 {(a.batch, a.out_channels, oh, ow)} on x's device")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
+    a.x = ctypes.c_void_p(x.data_ptr())
+    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
+    g.chunk_pixels = int(chunk_pixels)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_stem_wgrad_workspace_size_f32(ctypes.byref(g), ctypes.byref(n)),
+               "mcgmil_stem_wgrad_workspace_size_f32")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
+    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(L.mcgmil_stem_wgrad_f32(ctypes.byref(g), stream), "mcgmil_stem_wgrad_f32")
+    return dw
+
+
+def stem_conv_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """layer(x) through the differentiable op torch.ops.mcgmil.stem_conv_f32 (mcgmil.library)."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    return torch.ops.mcgmil.stem_conv_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
+
+
 def _native_conv(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
     """"bf16" (conv2d), "f32" (conv2d_f32) or None (the torch layer) for conv on x."""
     if isinstance(conv, nn.Conv2d):
@@ -533,12 +636,16 @@ def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """The backbone's convolution: the bf16 MFMA kernel when `conv_fusable`, the fp32 one when
     `conv32_fusable`, else the torch layer. Inside native_conv_training() a convolution under
     autograd that is `conv32_trainable` goes to the differentiable op instead of the torch layer
-    (the activation is made channels-last first if it is not: once, after the stem)."""
-    if _native_training and isinstance(layer, nn.Conv2d) and torch.is_grad_enabled() and \
-            (x.requires_grad or layer.weight.requires_grad) and x.is_cuda and x.dim() == 4:
+    (the activation is made channels-last first if it is not: once, after the stem). Inside
+    native_stem_conv_training() the same holds for a `stem_conv_trainable` convolution (1..4 input
+    channels: the stem) and torch.ops.mcgmil.stem_conv_f32."""
+    if (_native_training or _native_stem_conv_training) and isinstance(layer, nn.Conv2d) and \
+            torch.is_grad_enabled() and (x.requires_grad or layer.weight.requires_grad) and x.is_cuda and x.dim() == 4:
         xc = x.contiguous(memory_format=torch.channels_last)
-        if conv32_trainable(layer, xc):
+        if _native_training and conv32_trainable(layer, xc):
             return conv2d_f32_op(layer, xc)
+        if _native_stem_conv_training and stem_conv_trainable(layer, xc):
+            return stem_conv_f32_op(layer, xc)
     if isinstance(layer, nn.Conv2d) and conv_fusable(layer, x):
         return conv2d(layer, x)
     if isinstance(layer, nn.Conv2d) and conv32_fusable(layer, x):

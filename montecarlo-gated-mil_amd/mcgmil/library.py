@@ -19,6 +19,9 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.bn_pool_f32_backward(z, argmax, dy, weight?, mean, invstd, k, stride, pad, need_dz,
                                           need_dw) -> (dz, dweight, dbias)
 
+    torch.ops.mcgmil.stem_conv_f32(x, weight, stride, pad) -> y
+    torch.ops.mcgmil.stem_conv_f32_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -49,6 +52,12 @@ differentiable in z, weight and bias; its formula saves only z, argmax, mean, in
 (features.batchnorm_pool_backward, include/mcgmil_pool_grad.h), which has no formula itself.
 Gradients flowing into mean, invstd and argmax are ignored.
 
+stem_conv_f32 is the convolution with 1..4 input channels (features.stem_conv_trainable: the 7x7
+stride-2 stem): its forward is features.conv2d_f32 in the gather mode, bitwise what the inference
+path gives; its formula calls stem_conv_f32_backward, whose dW always comes from the HIP kernel of
+include/mcgmil_stem_grad.h (features.conv2d_f32_stem_wgrad) and whose dX, only when asked for (the
+model never does), from aten.convolution_backward. stem_conv_f32_backward has no formula itself.
+
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
@@ -62,7 +71,8 @@ import torch
 from . import features, ops
 
 __all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
-           "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward"]
+           "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward",
+           "stem_conv_f32", "stem_conv_f32_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -355,3 +365,48 @@ def _bn_pool_backward(ctx, dy, dmean, dinvstd, dargmax):
 
 
 bn_pool_f32.register_autograd(_bn_pool_backward, setup_context=_bn_pool_setup_context)
+
+
+def _stem_conv_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
+    """(shim, x channels-last) for the stem convolution's entry points, or ValueError."""
+    x = x.detach().contiguous(memory_format=torch.channels_last)
+    conv = features._ConvShim(weight, stride, pad)
+    reason = features.stem_conv_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"mcgmil::stem_conv_f32: {reason} (features.stem_conv_trainable)")
+    return conv, x
+
+
+@torch.library.custom_op("mcgmil::stem_conv_f32", mutates_args=())
+def stem_conv_f32(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    with torch.no_grad():
+        conv, xc = _stem_conv_shim(x, weight, stride, pad)
+        return features.conv2d_f32(conv, xc)
+
+
+stem_conv_f32.register_fake(_conv2d_f32_fake)
+
+
+@torch.library.custom_op("mcgmil::stem_conv_f32_backward", mutates_args=())
+def stem_conv_f32_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
+                           need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        conv, xc = _stem_conv_shim(x, weight, stride, pad)
+        dy = dy.detach().contiguous(memory_format=torch.channels_last)
+        dw = features.conv2d_f32_stem_wgrad(conv, xc, dy) if need_dw else weight.new_empty((0,))
+        # no native data gradient: the model never asks for one (the instances do not require grad)
+        dx = features._aten_conv_backward(conv, xc, dy, True, False)[0] if need_dx else x.new_empty((0,))
+    return dx, dw
+
+
+stem_conv_f32_backward.register_fake(_conv2d_f32_backward_fake)
+
+
+def _stem_conv_backward(ctx, dy):
+    x, weight = ctx.saved_tensors
+    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dx, dw = torch.ops.mcgmil.stem_conv_f32_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
+    return dx if need_dx else None, dw if need_dw else None, None, None
+
+
+stem_conv_f32.register_autograd(_stem_conv_backward, setup_context=_conv_setup_context)

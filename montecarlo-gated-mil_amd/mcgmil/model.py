@@ -22,7 +22,8 @@ What differs, by design:
     norm=True the blocks' BatchNorm / residual add / ReLU to the fused HIP op
     (torch.ops.mcgmil.bn_act_f32; include/mcgmil_bn_grad.h is its backward), and with stem=True
     the stem's BatchNorm / ReLU / max-pool to torch.ops.mcgmil.bn_pool_f32
-    (include/mcgmil_pool_grad.h). Without the opt-in, forward() in train mode raises instead of
+    (include/mcgmil_pool_grad.h), and with stem_conv=True the 7x7 stem convolution to
+    torch.ops.mcgmil.stem_conv_f32 (include/mcgmil_stem_grad.h is its weight gradient). Without the opt-in, forward() in train mode raises instead of
     silently running elsewhere.
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
@@ -104,6 +105,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._backbone_training = False
         self._norm_training = False
         self._stem_training = False
+        self._stem_conv_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -239,7 +241,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._head_training = bool(flag)
         return self
 
-    def enable_backbone_training(self, flag=True, *, norm=False, stem=False):
+    def enable_backbone_training(self, flag=True, *, norm=False, stem=False, stem_conv=False):
         """With enable_head_training(): forward() in train mode runs the backbone's block
         convolutions (every features.conv32_trainable one: all but the 3-channel stem) through
         the differentiable op torch.ops.mcgmil.conv2d_f32 instead of the torch layer: the fp32
@@ -258,12 +260,18 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         the fused HIP forward, which keeps one byte per pooled element instead of the ReLU output
         and the pool's int64 indices, and the HIP backward of include/mcgmil_pool_grad.h (timings
         in DESIGN.md §4). stem does not depend on norm; it only needs the flag itself. The 7x7
-        convolution's forward and backward stay on torch either way, because
-        features.conv32_trainable refuses 3 input channels. Off by default, norm and stem off by
-        default; returns self."""
+        convolution stays on the torch layer (features.conv32_trainable refuses 3 input
+        channels), unless stem_conv=True: then it runs, when features.stem_conv_trainable, through
+        the differentiable op torch.ops.mcgmil.stem_conv_f32: the gather-mode fp32 HIP forward
+        kernel the inference path uses, and the HIP weight gradient of include/mcgmil_stem_grad.h
+        (no data gradient: the instances do not require grad), instead of MIOpen in batch chunks
+        and a torch.cat (timings in DESIGN.md §4). stem_conv depends on neither norm nor stem; it
+        only needs the flag itself. Off by default, norm, stem and stem_conv off by default;
+        returns self."""
         self._backbone_training = bool(flag)
         self._norm_training = bool(flag) and bool(norm)
         self._stem_training = bool(flag) and bool(stem)
+        self._stem_conv_training = bool(flag) and bool(stem_conv)
         return self
 
     def _live_head(self):
@@ -316,7 +324,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                                           "(or opt in with enable_head_training())")
             with features.native_conv_training(self._backbone_training), \
                     features.native_norm_training(self._norm_training), \
-                    features.native_stem_training(self._stem_training):
+                    features.native_stem_training(self._stem_training), \
+                    features.native_stem_conv_training(self._stem_conv_training):
                 H = self.extract_features(x)
             Y, A = self.forward_features(H, T=1, seed=seed)
             Y, A = Y[0], A[0]
