@@ -12,8 +12,9 @@
  *
  * with zero padding: a GEMM with M = out_channels, N = kernel_h * kernel_w * in_channels and
  * K = batch * OH * OW output pixels on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulation).
- * The data gradient of a stride-1 convolution needs no entry point of its own: it is
- * mcgmil_conv2d_f32 of dY with the taps flipped and the channel axes swapped.
+ * The data gradient has its own entry point in mcgmil_conv_dgrad.h (mcgmil_conv2d_dgrad_f32, stride
+ * 1 and 2); for stride 1 it is also mcgmil_conv2d_f32 of dY with the taps flipped and the channel
+ * axes swapped.
  *
  * Determinism: no floating-point atomics. K is cut into granules of MCGMIL_WGRAD_GRANULE_PIXELS
  * consecutive output pixels; each (output tile, granule) writes one partial sum to the workspace

@@ -63,6 +63,8 @@ POOL_GRAD_EXPORTED = ("mcgmil_batchnorm_pool_train", "mcgmil_bn_pool_grad_args_s
 # include/mcgmil_stem_grad.h (the stem convolution's weight gradient, on mcgmil_conv_grad_args;
 # additive as well)
 STEM_GRAD_EXPORTED = ("mcgmil_stem_wgrad_workspace_size_f32", "mcgmil_stem_wgrad_f32")
+# include/mcgmil_conv_dgrad.h (the fp32 convolution's direct data gradient; additive as well)
+CONV_DGRAD_EXPORTED = ("mcgmil_conv_dgrad_args_size", "mcgmil_conv_dgrad_classes", "mcgmil_conv2d_dgrad_f32")
 
 _vp = ctypes.c_void_p
 
@@ -144,6 +146,11 @@ class ConvGradArgs(ctypes.Structure):
 
 
 WGRAD_GRANULE_PIXELS = 2048        # MCGMIL_WGRAD_GRANULE_PIXELS
+
+
+class ConvDgradArgs(ctypes.Structure):
+    """Mirror of struct mcgmil_conv_dgrad_args (include/mcgmil_conv_dgrad.h)."""
+    _fields_ = [("fwd", ConvArgs), ("dy", _vp), ("w_t", _vp), ("dx", _vp), ("reserved", ctypes.c_int64)]
 
 
 class BnGradArgs(ctypes.Structure):
@@ -325,6 +332,16 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")
+    pcd = ctypes.POINTER(ConvDgradArgs)
+    L.mcgmil_conv_dgrad_args_size.restype = ctypes.c_size_t
+    L.mcgmil_conv_dgrad_classes.argtypes = [pcd, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_int64)]
+    L.mcgmil_conv_dgrad_classes.restype = ctypes.c_int
+    L.mcgmil_conv2d_dgrad_f32.argtypes = [pcd, _vp]
+    L.mcgmil_conv2d_dgrad_f32.restype = ctypes.c_int
+    if L.mcgmil_conv_dgrad_args_size() != ctypes.sizeof(ConvDgradArgs):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_dgrad_args)={L.mcgmil_conv_dgrad_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(ConvDgradArgs)} bytes")
     pbg = ctypes.POINTER(BnGradArgs)
     L.mcgmil_bn_grad_args_size.restype = ctypes.c_size_t
     L.mcgmil_bn_grad_workspace_size.argtypes = [pbg, ctypes.POINTER(ctypes.c_size_t)]

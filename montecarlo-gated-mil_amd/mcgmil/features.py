@@ -30,8 +30,9 @@ Training (opt-in, MultiHeadGatedAttentionMIL.enable_backbone_training): inside
 `native_conv_training()` `run_conv` sends a `conv32_trainable` convolution that autograd tracks to
 torch.ops.mcgmil.conv2d_f32 (mcgmil.library). `conv2d_f32_wgrad` is the HIP weight gradient
 (include/mcgmil_conv_grad.h), `conv2d_f32_dgrad` the data gradient (the forward kernel on the
-flipped weight for stride 1), `conv2d_f32_backward` the op's backward on the route
-`conv_grad_native()` names (MCGMIL_CONV_GRAD=native; default aten.convolution_backward).
+flipped weight for stride 1), `conv2d_f32_dgrad_direct` the direct data-gradient kernel for stride 1
+and 2 (include/mcgmil_conv_dgrad.h), `conv2d_f32_backward` the op's backward on the route
+`conv_grad_route()` names (MCGMIL_CONV_GRAD=native or direct; default aten.convolution_backward).
 Inside `native_norm_training()` (enable_backbone_training(norm=True)) `bn_act` sends a pool-free
 `bn_trainable` BatchNorm (+ residual add) (+ ReLU) that autograd tracks to
 torch.ops.mcgmil.bn_act_f32: `batchnorm_act_stats` is its forward (mcgmil_batchnorm_act, which also
@@ -443,14 +444,77 @@ def conv2d_f32_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x_shape, x: Optional[tor
     return dx.contiguous(memory_format=torch.channels_last)
 
 
+def conv_grad_route() -> str:
+    """Which backward torch.ops.mcgmil.conv2d_f32 takes, from MCGMIL_CONV_GRAD: "aten" (the
+    default, also for an unset or unknown value): aten.convolution_backward (MIOpen) for both
+    gradients; "native": the HIP weight gradient and, for stride 1, the forward kernel on the
+    flipped weight as data gradient (stride 2: aten); "direct": the HIP weight gradient and the
+    direct HIP data gradient (conv2d_f32_dgrad_direct, include/mcgmil_conv_dgrad.h) for stride 1
+    and stride 2 alike -- no gradient of the convolution leaves the project's kernels. The forward
+    stays on the HIP kernel on every route."""
+    route = os.environ.get("MCGMIL_CONV_GRAD", "aten")
+    return route if route in ("native", "direct") else "aten"
+
+
 def conv_grad_native() -> bool:
-    """Which backward torch.ops.mcgmil.conv2d_f32 takes. MCGMIL_CONV_GRAD=native: the HIP weight
-    gradient and, for stride 1, the forward kernel as data gradient. Default ("aten"):
+    """Whether the weight gradient of torch.ops.mcgmil.conv2d_f32 comes from the HIP kernel:
+    MCGMIL_CONV_GRAD=native (with, for stride 1, the forward kernel as data gradient) or =direct
+    (with the direct data-gradient kernel; conv_grad_route). Default ("aten"):
     aten.convolution_backward (MIOpen) for both -- the measured-fastest for every ResNet-18 / -50
     shape class at 64 and 256 instances ("Backbone convolution backward"); the
     forward stays on the HIP kernel either way. Tensors of 2^31 bytes or more always take the
     native kernels where there is one (64-bit offsets)."""
-    return os.environ.get("MCGMIL_CONV_GRAD", "aten") == "native"
+    return conv_grad_route() in ("native", "direct")
+
+
+def dgrad_direct_supported(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
+    """Whether conv2d_f32_dgrad_direct implements this convolution's data gradient for dy: a CUDA
+    fp32 dy [batch, out_channels, OH, OW] without autocast, and a bias-free groups=1 dilation-1
+    zero-padded convolution with kernel 1..7 per axis, stride 1 or 2, pad < kernel,
+    in_channels % 16 == 0 and out_channels % 64 == 0 (include/mcgmil_conv_dgrad.h)."""
+    if not (conv32_enabled() and isinstance(conv, nn.Conv2d) and dy.is_cuda and dy.dim() == 4):
+        return False
+    if dy.dtype != torch.float32 or conv.weight.dtype != torch.float32 or torch.is_autocast_enabled("cuda"):
+        return False
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return False
+    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
+            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
+        return False
+    kh, kw = conv.kernel_size
+    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
+        return False
+    return conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0 and dy.shape[1] == conv.out_channels and \
+        dy.numel() > 0
+
+
+def conv2d_f32_dgrad_direct(conv: nn.Conv2d, dy: torch.Tensor, x_shape) -> torch.Tensor:
+    """dX (channels-last fp32, shape x_shape) of conv(x) given dY on the direct HIP data-gradient
+    kernel mcgmil_conv2d_dgrad_f32, stride 1 and 2: the residue classes of the input pixels, each
+    a stride-1 implicit GEMM over its own taps (include/mcgmil_conv_dgrad.h). The weight goes in
+    as one weight.permute(2, 3, 0, 1).contiguous(); every element of dX is written exactly once,
+    so two calls agree bitwise. Raises for anything dgrad_direct_supported refuses."""
+    if not dgrad_direct_supported(conv, dy):
+        raise ValueError("conv2d_f32_dgrad_direct needs a CUDA fp32 dy and a convolution the data-gradient "
+                         "kernel implements (see dgrad_direct_supported)")
+    L = _lib.load()
+    g = _lib.ConvDgradArgs()
+    a = g.fwd
+    a.batch, cin, a.height, a.width = (int(v) for v in x_shape)
+    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
+    a.kernel_h, a.kernel_w = conv.kernel_size
+    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
+    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
+    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
+    if cin != conv.in_channels or tuple(dy.shape) != (a.batch, a.out_channels, oh, ow):
+        raise ValueError(f"x_shape {tuple(x_shape)} does not belong to this convolution and dy {tuple(dy.shape)}")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    wt = conv.weight.detach().permute(2, 3, 0, 1).contiguous()           # [kh][kw][out][in]
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last)
+    g.dy, g.w_t, g.dx = (ctypes.c_void_p(t.data_ptr()) for t in (dy, wt, dx))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)
+    _lib.check(L.mcgmil_conv2d_dgrad_f32(ctypes.byref(g), stream), "mcgmil_conv2d_dgrad_f32")
+    return dx
 
 
 def _aten_conv_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool, need_dw: bool):
@@ -476,10 +540,14 @@ def _aten_conv_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need
 def conv2d_f32_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool = True,
                         need_dw: bool = True):
     """(dX or None, dW or None) of conv(x) given dY for a `conv32_trainable` convolution, on the
-    route conv_grad_native() names: the backward of torch.ops.mcgmil.conv2d_f32."""
+    route conv_grad_route() names: the backward of torch.ops.mcgmil.conv2d_f32."""
     if not conv32_trainable(conv, x):
         raise ValueError("conv2d_f32_backward needs a convolution and activation as conv32_trainable")
     dy = dy.contiguous(memory_format=torch.channels_last)
+    if conv_grad_route() == "direct":       # both gradients on the HIP kernels, whatever the size
+        dw = conv2d_f32_wgrad(conv, x, dy) if need_dw else None
+        dx = conv2d_f32_dgrad_direct(conv, dy, x.shape) if need_dx else None
+        return dx, dw
     big = 4 * max(x.numel(), dy.numel()) >= 2 ** 31
     if not (conv_grad_native() or big):
         return _aten_conv_backward(conv, x, dy, need_dx, need_dw)

@@ -29,8 +29,9 @@ autograd formula, so a backward of the backward raises. conv2d_f32 is the backbo
 convolution (features.conv2d_f32: x fp32 NCHW-shaped, channels-last in memory; weight
 [out, in, kh, kw]) made differentiable in x and weight the same way: its formula calls
 conv2d_f32_backward (features.conv2d_f32_backward: the HIP weight gradient and the forward kernel
-as data gradient with MCGMIL_CONV_GRAD=native, else aten.convolution_backward -- the
-measured-fastest today), which has none itself. A gradient that is not needed comes
+as data gradient with MCGMIL_CONV_GRAD=native, the HIP weight gradient and the direct HIP data
+gradient of include/mcgmil_conv_dgrad.h with MCGMIL_CONV_GRAD=direct, else
+aten.convolution_backward -- the measured-fastest today), which has none itself. A gradient that is not needed comes
 back as an empty tensor.
 
 bn_act_f32 is the blocks' relu?(batch_norm(x) [+ residual]) on the batch statistics of x (fp32,

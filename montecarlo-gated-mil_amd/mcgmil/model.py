@@ -245,10 +245,12 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         """With enable_head_training(): forward() in train mode runs the backbone's block
         convolutions (every features.conv32_trainable one: all but the 3-channel stem) through
         the differentiable op torch.ops.mcgmil.conv2d_f32 instead of the torch layer: the fp32
-        MFMA forward kernel, and for the backward the route features.conv_grad_native() names
+        MFMA forward kernel, and for the backward the route features.conv_grad_route() names
         (MCGMIL_CONV_GRAD=native: the HIP weight gradient and the forward kernel again as the
-        stride-1 data gradient; default: aten.convolution_backward, which measured faster on
-        every ResNet shape class). The stem, BatchNorm, ReLU, the pools and the
+        stride-1 data gradient; MCGMIL_CONV_GRAD=direct: the HIP weight gradient and the direct
+        HIP data gradient of include/mcgmil_conv_dgrad.h for stride 1 and 2, so that no gradient
+        of these convolutions leaves the project's kernels; default: aten.convolution_backward,
+        whose step measured fastest). The stem, BatchNorm, ReLU, the pools and the
         residual add stay on the torch layers, unless norm=True: then every pool-free
         features.bn_trainable BatchNorm of the blocks (fp32, batch statistics, no running-statistics
         update pending), with the residual add and ReLU that follow it, runs through the
