@@ -66,6 +66,10 @@ STEM_GRAD_EXPORTED = ("mcgmil_stem_wgrad_workspace_size_f32", "mcgmil_stem_wgrad
 # include/mcgmil_conv_dgrad.h (the fp32 convolution's direct data gradient; additive as well)
 CONV_DGRAD_EXPORTED = ("mcgmil_conv_dgrad_args_size", "mcgmil_conv_dgrad_classes", "mcgmil_conv2d_dgrad_f32")
 
+# include/mcgmil_conv_grad_bf16.h (the bf16 convolution's weight gradient; additive as well)
+CONV_GRAD_BF16_EXPORTED = ("mcgmil_conv_grad_bf16_args_size", "mcgmil_conv_wgrad_workspace_size_bf16",
+                           "mcgmil_conv2d_wgrad_bf16")
+
 _vp = ctypes.c_void_p
 
 
@@ -146,6 +150,15 @@ class ConvGradArgs(ctypes.Structure):
 
 
 WGRAD_GRANULE_PIXELS = 2048        # MCGMIL_WGRAD_GRANULE_PIXELS
+
+
+class ConvGradBf16Args(ctypes.Structure):
+    """Mirror of struct mcgmil_conv_grad_bf16_args (include/mcgmil_conv_grad_bf16.h)."""
+    _fields_ = [
+        ("fwd", ConvArgs), ("dy", _vp), ("dw", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+        ("chunk_pixels", ctypes.c_int64), ("reserved", ctypes.c_int64),
+    ]
 
 
 class ConvDgradArgs(ctypes.Structure):
@@ -332,6 +345,15 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")
+    pcb = ctypes.POINTER(ConvGradBf16Args)
+    L.mcgmil_conv_grad_bf16_args_size.restype = ctypes.c_size_t
+    L.mcgmil_conv_wgrad_workspace_size_bf16.argtypes = [pcb, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_conv_wgrad_workspace_size_bf16.restype = ctypes.c_int
+    L.mcgmil_conv2d_wgrad_bf16.argtypes = [pcb, _vp]
+    L.mcgmil_conv2d_wgrad_bf16.restype = ctypes.c_int
+    if L.mcgmil_conv_grad_bf16_args_size() != ctypes.sizeof(ConvGradBf16Args):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_bf16_args)={L.mcgmil_conv_grad_bf16_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(ConvGradBf16Args)} bytes")
     pcd = ctypes.POINTER(ConvDgradArgs)
     L.mcgmil_conv_dgrad_args_size.restype = ctypes.c_size_t
     L.mcgmil_conv_dgrad_classes.argtypes = [pcd, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),

@@ -47,6 +47,14 @@ Inside `native_stem_conv_training()` (enable_backbone_training(stem_conv=True)) 
 `stem_conv_trainable` convolution (1..4 input channels: the 7x7 stem) that autograd tracks to
 torch.ops.mcgmil.stem_conv_f32: `conv2d_f32` in its gather mode is the forward,
 `conv2d_f32_stem_wgrad` the HIP weight gradient (include/mcgmil_stem_grad.h).
+Mixed precision (opt-in, MultiHeadGatedAttentionMIL.enable_bf16_backbone_training): inside
+`native_conv_bf16_training()` `run_conv` sends a `conv_bf16_trainable` convolution that autograd
+tracks (a bf16 activation, as the blocks see it under torch.autocast) to
+torch.ops.mcgmil.conv2d_bf16: `conv2d_bf16` is the forward (the bf16 MFMA kernel of `conv2d`),
+`conv2d_bf16_wgrad` the bf16 HIP weight gradient with fp32 output
+(include/mcgmil_conv_grad_bf16.h), `conv2d_bf16_dgrad` the data gradient (the forward kernel on the
+flipped weight for stride 1, else aten), `conv2d_bf16_backward` the op's backward on the route
+MCGMIL_CONV_GRAD names (native or direct: the HIP kernels; default aten.convolution_backward).
 """
 import contextlib
 import ctypes
@@ -181,6 +189,13 @@ def conv2d(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
     if not conv_fusable(conv, x):
         raise ValueError("conv2d needs a CUDA channels-last bf16 activation, a bias-free groups=1 "
                          "convolution with 64k channels and no autograd (see conv_fusable)")
+    return _conv2d(conv, x, stats, in_ab, in_relu, flags)
+
+
+def _conv2d(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
+            in_ab: Optional[torch.Tensor] = None, in_relu: bool = True, flags: int = 0):
+    """conv2d without its predicate: for callers that have checked the domain themselves (conv2d
+    after conv_fusable, conv2d_bf16 after conv_bf16_trainable)."""
     L = _lib.load()
     a = _conv_args(conv, x)
     a.flags = int(flags)
@@ -664,6 +679,173 @@ def stem_conv_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     return torch.ops.mcgmil.stem_conv_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
 
 
+# ---------------------------------------------------------------- bf16 convolution backward
+_native_bf16_training = False
+
+
+@contextlib.contextmanager
+def native_conv_bf16_training(flag: bool = True):
+    """Inside this context `run_conv` sends every `conv_bf16_trainable` convolution that autograd
+    tracks (a bf16 activation: the blocks under torch.autocast("cuda", torch.bfloat16)) to the
+    differentiable op torch.ops.mcgmil.conv2d_bf16: the bf16 MFMA forward kernel and, on the native
+    route, the bf16 HIP weight gradient of include/mcgmil_conv_grad_bf16.h. Off outside it: the
+    opt-in of MultiHeadGatedAttentionMIL.enable_bf16_backbone_training."""
+    global _native_bf16_training
+    before, _native_bf16_training = _native_bf16_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_bf16_training = before
+
+
+def conv_bf16_untrainable_reason(conv: nn.Conv2d, x: torch.Tensor) -> Optional[str]:
+    """Why conv on x is not a convolution whose forward AND weight gradient run on the bf16 HIP
+    kernels (mcgmil_conv2d, include/mcgmil_conv_grad_bf16.h), or None when it is: a CUDA
+    channels-last bf16 activation below 2 GiB, an fp32 (master) or bf16 weight, a bias-free groups=1
+    dilation-1 zero-padded convolution with kernel 1..7, stride 1 or 2, pad < kernel and
+    in_channels and out_channels multiples of 64. Says nothing about autograd or autocast."""
+    if not conv_enabled():
+        return "the native convolutions are switched off (MCGMIL_NATIVE_CONV)"
+    if not isinstance(conv, nn.Conv2d):
+        return "not an nn.Conv2d"
+    if not (x.is_cuda and x.dim() == 4):
+        return "the activation is not a 4-d CUDA tensor"
+    if x.dtype != torch.bfloat16:
+        return "the activation must be bf16"
+    if conv.weight.dtype not in (torch.float32, torch.bfloat16):
+        return "the weight must be fp32 or bf16"
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return "only a bias-free groups=1 zero-padded convolution"
+    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
+            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
+        return "dilation 1, a square stride of 1 or 2 and a square integer padding"
+    kh, kw = conv.kernel_size
+    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
+        return "kernel 1..7 per axis and pad < min(kh, kw)"
+    if conv.in_channels % 64:
+        return "in_channels must be a multiple of 64"
+    if conv.out_channels % 64:
+        return "out_channels must be a multiple of 64"
+    if x.shape[1] != conv.in_channels:
+        return "the activation's channels are not the convolution's in_channels"
+    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
+        return "the activation must be non-empty and channels-last"
+    s, p = _square(conv.stride), _square(conv.padding)
+    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
+    if not (oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256):
+        return "batch * OH * OW must be in 1 .. 2^31 - 257"
+    if x.numel() * 2 >= 2 ** 31 or max(x.shape[2], x.shape[3]) > 16383:
+        return "the activation must be smaller than 2 GiB, height and width at most 16383"
+    return None
+
+
+def conv_bf16_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
+    """conv_bf16_untrainable_reason(conv, x) is None. Says nothing about autograd."""
+    return conv_bf16_untrainable_reason(conv, x) is None
+
+
+def conv2d_bf16(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """conv(x) on the bf16 MFMA kernel for a `conv_bf16_trainable` convolution: what conv2d gives,
+    bit for bit, without conv2d's autocast and autograd clauses (the weight, fp32 master or bf16,
+    goes through mcgmil_pack_conv_weights). The forward of torch.ops.mcgmil.conv2d_bf16."""
+    reason = conv_bf16_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_bf16: {reason} (see conv_bf16_trainable)")
+    return _conv2d(conv, x)
+
+
+def conv2d_bf16_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
+    """dW [out, in, kh, kw] fp32 of conv(x) given dY (both bf16), on the bf16 HIP weight-gradient
+    kernel (mcgmil_conv2d_wgrad_bf16; see conv_bf16_trainable): bf16 operands, fp32 accumulation.
+    chunk_pixels caps the output pixels per launch chunk (0: the library's default); the result
+    does not depend on it, bitwise."""
+    reason = conv_bf16_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_bf16_wgrad: {reason} (see conv_bf16_trainable)")
+    L = _lib.load()
+    g = _lib.ConvGradBf16Args()
+    a = g.fwd
+    a.batch, _, a.height, a.width = x.shape
+    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
+    a.kernel_h, a.kernel_w = conv.kernel_size
+    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
+    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
+    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
+    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.bfloat16 or dy.device != x.device:
+        raise ValueError(f"dy must be bf16 {(a.batch, a.out_channels, oh, ow)} on x's device")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
+    a.x = ctypes.c_void_p(x.data_ptr())
+    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
+    g.chunk_pixels = int(chunk_pixels)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_conv_wgrad_workspace_size_bf16(ctypes.byref(g), ctypes.byref(n)),
+               "mcgmil_conv_wgrad_workspace_size_bf16")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
+    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(L.mcgmil_conv2d_wgrad_bf16(ctypes.byref(g), stream), "mcgmil_conv2d_wgrad_bf16")
+    return dw
+
+
+def dgrad_bf16_native(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
+    """Whether conv2d_bf16_dgrad runs this convolution's data gradient on the bf16 forward kernel:
+    stride 1, a square kernel (one pad k - 1 - p for both axes) and a dY below 2 GiB (the forward
+    kernel's input limit). Otherwise aten.convolution_backward: there is no bf16 direct or strided
+    data-gradient kernel."""
+    return _square(conv.stride) == 1 and conv.kernel_size[0] == conv.kernel_size[1] and dy.numel() * 2 < 2 ** 31
+
+
+def _aten_conv_backward_bf16(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool, need_dw: bool):
+    """(dx, dw) from aten.convolution_backward on bf16 tensors (the weight cast as autocast casts
+    it); dw comes back in conv.weight's dtype."""
+    w = conv.weight.detach()
+    dx, dw = _aten_conv_backward(_ConvShim(w.to(torch.bfloat16), _square(conv.stride), _square(conv.padding)),
+                                 x, dy, need_dx, need_dw)
+    return dx, dw.to(w.dtype) if need_dw else None
+
+
+def conv2d_bf16_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """dX (channels-last bf16, x's shape) of conv(x) given dY. When dgrad_bf16_native: the bf16
+    forward kernel (mcgmil_conv2d) of dY with the flipped, channel-swapped weight
+    (flipped_weight), pad k - 1 - p -- fp32 accumulation and one rounding to bf16. Otherwise
+    aten.convolution_backward with output mask (True, False, False)."""
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if not dgrad_bf16_native(conv, dy):
+        return _aten_conv_backward_bf16(conv, x, dy, True, False)[0]
+    shim = _ConvShim(flipped_weight(conv.weight.detach()), 1, conv.kernel_size[0] - 1 - _square(conv.padding))
+    dx = conv2d_bf16(shim, dy)
+    if tuple(dx.shape) != tuple(x.shape):
+        raise ValueError(f"x {tuple(x.shape)} does not belong to this convolution and dy {tuple(dy.shape)}")
+    return dx
+
+
+def conv2d_bf16_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool = True,
+                         need_dw: bool = True):
+    """(dX bf16 or None, dW in the weight's dtype or None) of conv(x) given dY for a
+    `conv_bf16_trainable` convolution: the backward of torch.ops.mcgmil.conv2d_bf16, on the route
+    MCGMIL_CONV_GRAD names (conv_grad_route, read on every call). "aten" (the default):
+    aten.convolution_backward on bf16 tensors for both gradients. "native": the bf16 HIP weight
+    gradient (conv2d_bf16_wgrad; fp32, so an fp32 master weight gets it unrounded) and
+    conv2d_bf16_dgrad. "direct" means "native" for this op: there is no bf16 direct data-gradient
+    kernel."""
+    reason = conv_bf16_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_bf16_backward: {reason} (see conv_bf16_trainable)")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if not conv_grad_native():
+        return _aten_conv_backward_bf16(conv, x, dy, need_dx, need_dw)
+    dw = conv2d_bf16_wgrad(conv, x, dy).to(conv.weight.dtype) if need_dw else None
+    dx = conv2d_bf16_dgrad(conv, dy, x) if need_dx else None
+    return dx, dw
+
+
+def conv2d_bf16_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """layer(x) through the differentiable op torch.ops.mcgmil.conv2d_bf16 (mcgmil.library)."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    return torch.ops.mcgmil.conv2d_bf16(x, layer.weight, _square(layer.stride), _square(layer.padding))
+
+
 def _native_conv(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
     """"bf16" (conv2d), "f32" (conv2d_f32) or None (the torch layer) for conv on x."""
     if isinstance(conv, nn.Conv2d):
@@ -706,10 +888,13 @@ def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     autograd that is `conv32_trainable` goes to the differentiable op instead of the torch layer
     (the activation is made channels-last first if it is not: once, after the stem). Inside
     native_stem_conv_training() the same holds for a `stem_conv_trainable` convolution (1..4 input
-    channels: the stem) and torch.ops.mcgmil.stem_conv_f32."""
-    if (_native_training or _native_stem_conv_training) and isinstance(layer, nn.Conv2d) and \
+    channels: the stem) and torch.ops.mcgmil.stem_conv_f32, and inside native_conv_bf16_training()
+    for a `conv_bf16_trainable` convolution (a bf16 activation) and torch.ops.mcgmil.conv2d_bf16."""
+    if (_native_training or _native_stem_conv_training or _native_bf16_training) and isinstance(layer, nn.Conv2d) and \
             torch.is_grad_enabled() and (x.requires_grad or layer.weight.requires_grad) and x.is_cuda and x.dim() == 4:
         xc = x.contiguous(memory_format=torch.channels_last)
+        if _native_bf16_training and conv_bf16_trainable(layer, xc):
+            return conv2d_bf16_op(layer, xc)
         if _native_training and conv32_trainable(layer, xc):
             return conv2d_f32_op(layer, xc)
         if _native_stem_conv_training and stem_conv_trainable(layer, xc):

@@ -22,6 +22,9 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.stem_conv_f32(x, weight, stride, pad) -> y
     torch.ops.mcgmil.stem_conv_f32_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
 
+    torch.ops.mcgmil.conv2d_bf16(x, weight, stride, pad) -> y
+    torch.ops.mcgmil.conv2d_bf16_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -59,6 +62,16 @@ path gives; its formula calls stem_conv_f32_backward, whose dW always comes from
 include/mcgmil_stem_grad.h (features.conv2d_f32_stem_wgrad) and whose dX, only when asked for (the
 model never does), from aten.convolution_backward. stem_conv_f32_backward has no formula itself.
 
+conv2d_bf16 is the block convolution in mixed precision (features.conv_bf16_trainable: x bf16
+NCHW-shaped, channels-last in memory; weight [out, in, kh, kw], the fp32 master or bf16; in and out
+channels multiples of 64): its forward is the bf16 MFMA kernel of features.conv2d, bit for bit; its
+formula calls conv2d_bf16_backward (features.conv2d_bf16_backward), which has none itself. With
+MCGMIL_CONV_GRAD=native the weight gradient is the bf16 HIP kernel of
+include/mcgmil_conv_grad_bf16.h (bf16 operands, fp32 accumulation, fp32 dW) and the stride-1 data
+gradient the forward kernel on the flipped weight (stride 2: aten, dx only); =direct means native
+here (there is no bf16 direct data-gradient kernel); else aten.convolution_backward on bf16
+tensors. dw comes back in the weight's dtype and contiguous, dx bf16 channels-last.
+
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
@@ -73,7 +86,7 @@ from . import features, ops
 
 __all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
            "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward",
-           "stem_conv_f32", "stem_conv_f32_backward"]
+           "stem_conv_f32", "stem_conv_f32_backward", "conv2d_bf16", "conv2d_bf16_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -411,3 +424,54 @@ def _stem_conv_backward(ctx, dy):
 
 
 stem_conv_f32.register_autograd(_stem_conv_backward, setup_context=_conv_setup_context)
+
+
+def _conv_bf16_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
+    """(shim, x channels-last) for the bf16 convolution's entry points, or ValueError."""
+    x = x.detach().contiguous(memory_format=torch.channels_last)
+    conv = features._ConvShim(weight, stride, pad)
+    reason = features.conv_bf16_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"mcgmil::conv2d_bf16: {reason} (features.conv_bf16_trainable)")
+    return conv, x
+
+
+@torch.library.custom_op("mcgmil::conv2d_bf16", mutates_args=())
+def conv2d_bf16(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+    with torch.no_grad():
+        conv, xc = _conv_bf16_shim(x, weight, stride, pad)
+        return features.conv2d_bf16(conv, xc)
+
+
+@conv2d_bf16.register_fake
+def _conv2d_bf16_fake(x, weight, stride, pad):
+    oh, ow = _conv_out_hw(x, weight, stride, pad)
+    return torch.empty((x.shape[0], weight.shape[0], oh, ow), dtype=torch.bfloat16, device=x.device,
+                       memory_format=torch.channels_last)
+
+
+@torch.library.custom_op("mcgmil::conv2d_bf16_backward", mutates_args=())
+def conv2d_bf16_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
+                         need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        conv, xc = _conv_bf16_shim(x, weight, stride, pad)
+        dx, dw = features.conv2d_bf16_backward(conv, xc, dy.detach().to(torch.bfloat16), need_dx, need_dw)
+    return (dx if need_dx else x.new_empty((0,))), (dw if need_dw else weight.new_empty((0,)))
+
+
+@conv2d_bf16_backward.register_fake
+def _conv2d_bf16_backward_fake(x, weight, dy, stride, pad, need_dx, need_dw):
+    dx = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last) \
+        if need_dx else x.new_empty((0,))
+    dw = weight.new_empty(weight.shape) if need_dw else weight.new_empty((0,))
+    return dx, dw
+
+
+def _conv_bf16_backward(ctx, dy):
+    x, weight = ctx.saved_tensors
+    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    dx, dw = torch.ops.mcgmil.conv2d_bf16_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
+    return dx if need_dx else None, dw if need_dw else None, None, None
+
+
+conv2d_bf16.register_autograd(_conv_bf16_backward, setup_context=_conv_setup_context)

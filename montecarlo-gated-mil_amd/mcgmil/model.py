@@ -106,6 +106,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._norm_training = False
         self._stem_training = False
         self._stem_conv_training = False
+        self._bf16_backbone_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -276,6 +277,22 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._stem_conv_training = bool(flag) and bool(stem_conv)
         return self
 
+    def enable_bf16_backbone_training(self, flag=True):
+        """With enable_head_training(): forward() in train mode runs the backbone in mixed
+        precision, under torch.autocast("cuda", torch.bfloat16), and sends the block convolutions
+        (every features.conv_bf16_trainable one: all 19 of ResNet-18 but the 3-channel stem)
+        through the differentiable op torch.ops.mcgmil.conv2d_bf16 instead of the torch layer: the
+        bf16 MFMA forward kernel of the inference path, and for the backward the route
+        MCGMIL_CONV_GRAD names (native or direct: the bf16 HIP weight gradient of
+        include/mcgmil_conv_grad_bf16.h, written in fp32 into the fp32 master weight's .grad, and
+        the forward kernel again as the stride-1 data gradient; default: aten.convolution_backward
+        on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
+        by layer, so the stem convolution, BatchNorm, ReLU and the pools are the torch layers under
+        autocast. The head stays fp32. Eval mode, no_grad and the default are unchanged. Off by
+        default; returns self."""
+        self._bf16_backbone_training = bool(flag)
+        return self
+
     def _live_head(self):
         """The head parameters stacked for the kernel WITH their autograd history."""
         lv, lu = self._gate_linears()
@@ -328,7 +345,11 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                     features.native_norm_training(self._norm_training), \
                     features.native_stem_training(self._stem_training), \
                     features.native_stem_conv_training(self._stem_conv_training):
-                H = self.extract_features(x)
+                if self._bf16_backbone_training:
+                    with torch.autocast("cuda", torch.bfloat16), features.native_conv_bf16_training():
+                        H = self.extract_features(x)
+                else:
+                    H = self.extract_features(x)
             Y, A = self.forward_features(H, T=1, seed=seed)
             Y, A = Y[0], A[0]
             aux = None
