@@ -70,6 +70,10 @@ CONV_DGRAD_EXPORTED = ("mcgmil_conv_dgrad_args_size", "mcgmil_conv_dgrad_classes
 CONV_GRAD_BF16_EXPORTED = ("mcgmil_conv_grad_bf16_args_size", "mcgmil_conv_wgrad_workspace_size_bf16",
                            "mcgmil_conv2d_wgrad_bf16")
 
+# include/mcgmil_bn_grad_bf16.h (the bf16 fused BatchNorm/add/ReLU's backward; additive as well)
+BN_GRAD_BF16_EXPORTED = ("mcgmil_bn_grad_bf16_args_size", "mcgmil_bn_grad_workspace_size_bf16",
+                         "mcgmil_batchnorm_act_backward_bf16")
+
 _vp = ctypes.c_void_p
 
 
@@ -177,6 +181,12 @@ class BnGradArgs(ctypes.Structure):
 
 
 BN_GRAD_PART_ELEMS = 32768         # MCGMIL_BN_GRAD_PART_ELEMS
+
+
+class BnGradBf16Args(ctypes.Structure):
+    """Mirror of struct mcgmil_bn_grad_bf16_args (include/mcgmil_bn_grad_bf16.h): the fields of
+    mcgmil_bn_grad_args, with bf16 x / y / dy / dx / dresidual."""
+    _fields_ = list(BnGradArgs._fields_)
 
 
 class BnPoolGradArgs(ctypes.Structure):
@@ -373,6 +383,15 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_bn_grad_args_size() != ctypes.sizeof(BnGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_grad_args)={L.mcgmil_bn_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(BnGradArgs)} bytes")
+    pbb = ctypes.POINTER(BnGradBf16Args)
+    L.mcgmil_bn_grad_bf16_args_size.restype = ctypes.c_size_t
+    L.mcgmil_bn_grad_workspace_size_bf16.argtypes = [pbb, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_bn_grad_workspace_size_bf16.restype = ctypes.c_int
+    L.mcgmil_batchnorm_act_backward_bf16.argtypes = [pbb, _vp]
+    L.mcgmil_batchnorm_act_backward_bf16.restype = ctypes.c_int
+    if L.mcgmil_bn_grad_bf16_args_size() != ctypes.sizeof(BnGradBf16Args):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_grad_bf16_args)={L.mcgmil_bn_grad_bf16_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(BnGradBf16Args)} bytes")
     ppg = ctypes.POINTER(BnPoolGradArgs)
     L.mcgmil_batchnorm_pool_train.argtypes = [pb, _vp, _vp]
     L.mcgmil_batchnorm_pool_train.restype = ctypes.c_int

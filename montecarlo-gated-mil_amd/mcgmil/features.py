@@ -55,6 +55,10 @@ torch.ops.mcgmil.conv2d_bf16: `conv2d_bf16` is the forward (the bf16 MFMA kernel
 (include/mcgmil_conv_grad_bf16.h), `conv2d_bf16_dgrad` the data gradient (the forward kernel on the
 flipped weight for stride 1, else aten), `conv2d_bf16_backward` the op's backward on the route
 MCGMIL_CONV_GRAD names (native or direct: the HIP kernels; default aten.convolution_backward).
+Inside `native_norm_bf16_training()` (enable_bf16_norm_training()) `bn_act` sends a
+pool-free `bn_bf16_trainable` BatchNorm (+ residual add) (+ ReLU) that autograd tracks to
+torch.ops.mcgmil.bn_act_bf16: `batchnorm_act_stats_bf16` is its forward (mcgmil_batchnorm_act in
+bf16), `batchnorm_act_backward_bf16` its HIP backward (include/mcgmil_bn_grad_bf16.h).
 """
 import contextlib
 import ctypes
@@ -1178,6 +1182,150 @@ def bn_act_f32_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
     return torch.ops.mcgmil.bn_act_f32(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
 
 
+# ---------------------------------------------------------------- fused bf16 BatchNorm backward
+_native_norm_bf16_training = False
+
+
+@contextlib.contextmanager
+def native_norm_bf16_training(flag: bool = True):
+    """Inside this context `bn_act` sends every pool-free `bn_bf16_trainable` BatchNorm (+ residual
+    add) (+ ReLU) that autograd tracks (a bf16 activation: the blocks under
+    torch.autocast("cuda", torch.bfloat16)) to the differentiable op torch.ops.mcgmil.bn_act_bf16
+    (the fused HIP forward in bf16 and the HIP backward of include/mcgmil_bn_grad_bf16.h). Off
+    outside it: the opt-in of MultiHeadGatedAttentionMIL.enable_bf16_norm_training()."""
+    global _native_norm_bf16_training
+    before, _native_norm_bf16_training = _native_norm_bf16_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_norm_bf16_training = before
+
+
+def bn_bf16_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why `bn_bf16_trainable` refuses (x, bn, residual), or None when it holds: the clauses of
+    `bn_untrainable_reason` with a bf16 activation and residual, fp32 (master) parameters or none,
+    and no autocast clause (the op takes what autocast gives it). The device is checked last, so
+    the other clauses can be seen on a machine without a GPU."""
+    if not isinstance(bn, nn.BatchNorm2d) or x.dim() != 4:
+        return "layer: an nn.BatchNorm2d on a 4-D activation"
+    if x.dtype != torch.bfloat16 or any(p is not None and p.dtype != torch.float32 for p in (bn.weight, bn.bias)):
+        return "dtype: a bf16 activation with fp32 parameters"
+    C = x.shape[1]
+    if C % 8 or C > 2048 or C != bn.num_features:
+        return "channels: C % 8 == 0, C <= 2048, C == bn.num_features"
+    if x.numel() < 2 * C:
+        return "rows: at least 2 values per channel"
+    if not _use_batch(bn):
+        return "statistics: running-statistics mode"
+    if bn.training and bn.track_running_stats and bn.running_mean is not None:
+        return "statistics: a running-statistics update is pending"     # torch would update them
+    if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or
+                                 residual.device != x.device):
+        return "residual: x's shape, dtype and device"
+    if not x.is_cuda or any(p is not None and p.device != x.device for p in (bn.weight, bn.bias)):
+        return "device: a CUDA activation with the parameters on its device"
+    return None
+
+
+def bn_bf16_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[torch.Tensor] = None) -> bool:
+    """A BatchNorm (+ residual add) (+ ReLU) whose forward AND backward run on the fused bf16 HIP
+    kernels: `bn_trainable` for a CUDA bf16 4-D activation (and residual) with fp32 parameters,
+    under autocast or not. `bn_bf16_untrainable_reason` names the clause that fails."""
+    return bn_bf16_untrainable_reason(x, bn, residual) is None
+
+
+def _check_rows_c_bf16(name: str, x: torch.Tensor, **like) -> None:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and
+            x.shape[1] <= 2048 and x.numel() >= 2 * x.shape[1] and
+            x.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError(f"{name} needs a CUDA channels-last bf16 [N, C, H, W] activation with C % 8 == 0, "
+                         "C <= 2048 and at least 2 values per channel")
+    for n, t in like.items():
+        if t is not None and (t.shape != x.shape or t.dtype != x.dtype or t.device != x.device or
+                              not t.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError(f"{name}: {n} must be channels-last with x's shape, dtype and device")
+
+
+def batchnorm_act_stats_bf16(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                             residual: Optional[torch.Tensor], eps: float, relu: bool):
+    """(y bf16, mean [C] fp32, invstd [C] fp32) of relu?(batch_norm(x) [+ residual]) on the batch
+    statistics of x (bf16, channels-last; weight and bias fp32): mcgmil_batchnorm_act with
+    MCGMIL_BF16, batch_mean / batch_invstd requested and the statistics from its own pass over x.
+    What the backward (batchnorm_act_backward_bf16) needs."""
+    _check_rows_c_bf16("batchnorm_act_stats_bf16", x, residual=residual)
+    L = _lib.load()
+    dev = x.device
+    N, C, H, W = x.shape
+    _check_per_channel("batchnorm_act_stats_bf16", C, dev, weight=weight, bias=bias)
+    y = torch.empty_like(x, memory_format=torch.channels_last)
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    invstd = torch.empty(C, dtype=torch.float32, device=dev)
+    a = _lib.BnArgs()
+    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_BF16
+    a.batch, a.height, a.width = N, H, W
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.x, a.y, a.residual = p(x), p(y), p(residual)
+    a.gamma, a.beta = p(weight), p(bias)
+    a.eps, a.relu = float(eps), int(bool(relu))
+    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
+    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), stream), "mcgmil_batchnorm_act")
+    return y, mean, invstd
+
+
+def batchnorm_act_backward_bf16(x: torch.Tensor, y: Optional[torch.Tensor], dy: torch.Tensor,
+                                weight: Optional[torch.Tensor], mean: torch.Tensor, invstd: torch.Tensor,
+                                relu: bool, need_dx: bool = True, need_dres: bool = False, need_dw: bool = True):
+    """(dx bf16, dresidual bf16, dweight fp32, dbias fp32), None where not needed, of
+    batchnorm_act_stats_bf16 given dy (mcgmil_batchnorm_act_backward_bf16,
+    include/mcgmil_bn_grad_bf16.h). y is the forward's output, read for the ReLU mask only (None
+    without ReLU). dresidual exists with ReLU only: without it the residual's gradient is dy itself
+    and the caller passes dy on."""
+    _check_rows_c_bf16("batchnorm_act_backward_bf16", x, y=y if relu else None, dy=dy)
+    if relu and y is None:
+        raise ValueError("batchnorm_act_backward_bf16: relu needs y (the forward's output)")
+    need_dres = bool(need_dres and relu)
+    if not (need_dx or need_dres or need_dw):
+        return None, None, None, None
+    L = _lib.load()
+    dev = x.device
+    N, C, H, W = x.shape
+    _check_per_channel("batchnorm_act_backward_bf16", C, dev, weight=weight, mean=mean, invstd=invstd)
+    dx = torch.empty_like(x, memory_format=torch.channels_last) if need_dx else None
+    dres = torch.empty_like(x, memory_format=torch.channels_last) if need_dres else None
+    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    a = _lib.BnGradBf16Args()
+    a.rows, a.channels, a.relu = N * H * W, C, int(bool(relu))
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.x, a.y, a.dy = p(x), p(y if relu else None), p(dy)
+    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
+    a.dx, a.dresidual, a.dgamma, a.dbeta = p(dx), p(dres), p(dw), p(db)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_grad_workspace_size_bf16(ctypes.byref(a), ctypes.byref(n)),
+               "mcgmil_bn_grad_workspace_size_bf16")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
+    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_act_backward_bf16(ctypes.byref(a), stream), "mcgmil_batchnorm_act_backward_bf16")
+    return dx, dres, dw, db
+
+
+def bn_act_bf16_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
+                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu?(bn(x) [+ residual]) through the differentiable op torch.ops.mcgmil.bn_act_bf16
+    (mcgmil.library); the activation and the residual are made channels-last first if they are not."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    x = x.contiguous(memory_format=torch.channels_last)
+    if residual is not None:
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    return torch.ops.mcgmil.bn_act_bf16(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
+
+
 # ---------------------------------------------------------------- fused stem BatchNorm / pool backward
 _native_stem_training = False
 
@@ -1322,13 +1470,16 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
     the torch layers (CPU, autograd, training with running-stat updates, odd layouts). Inside
     native_norm_training() a pool-free `bn_trainable` layer under autograd goes to the
     differentiable fused op instead of the torch layers; inside native_stem_training() a
-    residual-free `bn_pool_trainable` layer with a pool does."""
+    residual-free `bn_pool_trainable` layer with a pool does; inside native_norm_bf16_training()
+    a pool-free `bn_bf16_trainable` layer (a bf16 activation) goes to the bf16 fused op."""
     tracked = torch.is_grad_enabled() and isinstance(bn, nn.BatchNorm2d) and \
         (x.requires_grad or any(p.requires_grad for p in bn.parameters()))
     if _native_stem_training and pool is not None and residual is None and tracked and bn_pool_trainable(x, bn, pool):
         return bn_pool_f32_op(bn, x, relu, pool)
     if _native_norm_training and pool is None and tracked and bn_trainable(x, bn, residual):
         return bn_act_f32_op(bn, x, relu, residual)
+    if _native_norm_bf16_training and pool is None and tracked and bn_bf16_trainable(x, bn, residual):
+        return bn_act_bf16_op(bn, x, relu, residual)
     if fusable(x, bn, residual):
         if pool is None or (residual is None and _pool_params(pool) is not None):
             return batchnorm_act(x, bn, relu, residual, pool)

@@ -25,6 +25,10 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.conv2d_bf16(x, weight, stride, pad) -> y
     torch.ops.mcgmil.conv2d_bf16_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
 
+    torch.ops.mcgmil.bn_act_bf16(x, weight?, bias?, residual?, eps, relu) -> (y, mean, invstd)
+    torch.ops.mcgmil.bn_act_bf16_backward(x, y, dy, weight?, mean, invstd, relu, need_dx, need_dres,
+                                          need_dw) -> (dx, dres, dweight, dbias)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -72,6 +76,13 @@ gradient the forward kernel on the flipped weight (stride 2: aten, dx only); =di
 here (there is no bf16 direct data-gradient kernel); else aten.convolution_backward on bf16
 tensors. dw comes back in the weight's dtype and contiguous, dx bf16 channels-last.
 
+bn_act_bf16 is bn_act_f32 in mixed precision: x, residual and y bf16, weight and bias the fp32
+master parameters, mean and invstd fp32 (features.batchnorm_act_stats_bf16: mcgmil_batchnorm_act
+with MCGMIL_BF16). Its formula saves the same tensors and calls bn_act_bf16_backward
+(features.batchnorm_act_backward_bf16, include/mcgmil_bn_grad_bf16.h), which has no formula itself:
+dx and dres come back bf16, dweight and dbias fp32. Without ReLU the residual's gradient is dy
+itself; gradients flowing into mean and invstd are ignored.
+
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
@@ -86,7 +97,8 @@ from . import features, ops
 
 __all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
            "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward",
-           "stem_conv_f32", "stem_conv_f32_backward", "conv2d_bf16", "conv2d_bf16_backward"]
+           "stem_conv_f32", "stem_conv_f32_backward", "conv2d_bf16", "conv2d_bf16_backward",
+           "bn_act_bf16", "bn_act_bf16_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -311,6 +323,63 @@ def _bn_backward(ctx, dy, dmean, dinvstd):
 
 
 bn_act_f32.register_autograd(_bn_backward, setup_context=_bn_setup_context)
+
+
+@torch.library.custom_op("mcgmil::bn_act_bf16", mutates_args=())
+def bn_act_bf16(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                residual: Optional[torch.Tensor], eps: float, relu: bool
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+        return features.batchnorm_act_stats_bf16(_channels_last(x), f(weight), f(bias),
+                                                 None if residual is None else _channels_last(residual), eps, relu)
+
+
+@bn_act_bf16.register_fake
+def _bn_act_bf16_fake(x, weight, bias, residual, eps, relu):
+    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    return y, x.new_empty((x.shape[1],), dtype=torch.float32), x.new_empty((x.shape[1],), dtype=torch.float32)
+
+
+@torch.library.custom_op("mcgmil::bn_act_bf16_backward", mutates_args=())
+def bn_act_bf16_backward(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                         mean: torch.Tensor, invstd: torch.Tensor, relu: bool, need_dx: bool, need_dres: bool,
+                         need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        dx, dres, dw, db = features.batchnorm_act_backward_bf16(
+            _channels_last(x), _channels_last(y) if relu else None, _channels_last(dy.to(torch.bfloat16)),
+            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
+            invstd.detach().contiguous(), relu, need_dx, need_dres, need_dw)
+    e = lambda t, like: like.new_empty((0,)) if t is None else t  # noqa: E731
+    return e(dx, x), e(dres, x), e(dw, mean), e(db, mean)
+
+
+@bn_act_bf16_backward.register_fake
+def _bn_act_bf16_backward_fake(x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
+    full = lambda need: torch.empty(x.shape, dtype=torch.bfloat16, device=x.device,  # noqa: E731
+                                    memory_format=torch.channels_last) if need else x.new_empty((0,))
+    vec = lambda: mean.new_empty((x.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+    return full(need_dx), full(need_dres and relu), vec(), vec()
+
+
+def _bn_bf16_backward(ctx, dy, dmean, dinvstd):
+    # as _bn_backward: mean and invstd are by-products for the backward, not differentiable outputs
+    if dy is None:
+        return (None,) * 6
+    x, mean, invstd, *rest = ctx.saved_tensors
+    weight = rest.pop(0) if ctx.has_weight else None
+    y = rest.pop(0) if ctx.relu else x.new_empty((0,))
+    need = ctx.needs_input_grad
+    need_dx, need_dw, need_dres = need[0], need[1] or need[2], need[3]
+    dx, dres, dw, db = torch.ops.mcgmil.bn_act_bf16_backward(x, y, dy, weight, mean, invstd, ctx.relu, need_dx,
+                                                             need_dres and ctx.relu, need_dw)
+    if need_dres and not ctx.relu:
+        dres = dy
+    return (dx if need_dx else None, dw if need[1] else None, db if need[2] else None,
+            dres if need_dres else None, None, None)
+
+
+bn_act_bf16.register_autograd(_bn_bf16_backward, setup_context=_bn_setup_context)
 
 
 @torch.library.custom_op("mcgmil::bn_pool_f32", mutates_args=())

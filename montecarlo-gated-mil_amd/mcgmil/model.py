@@ -107,6 +107,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._stem_training = False
         self._stem_conv_training = False
         self._bf16_backbone_training = False
+        self._bf16_norm_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -288,9 +289,27 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         the forward kernel again as the stride-1 data gradient; default: aten.convolution_backward
         on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
         by layer, so the stem convolution, BatchNorm, ReLU and the pools are the torch layers under
-        autocast. The head stays fp32. Eval mode, no_grad and the default are unchanged. Off by
-        default; returns self."""
+        autocast, unless enable_bf16_norm_training() is on as well. The head stays fp32. Eval mode,
+        no_grad and the default are unchanged. Off by default; switching it off switches
+        enable_bf16_norm_training off too; returns self."""
         self._bf16_backbone_training = bool(flag)
+        if not flag:
+            self._bf16_norm_training = False
+        return self
+
+    def enable_bf16_norm_training(self, flag=True):
+        """On top of enable_bf16_backbone_training(), and in effect only while that is on: forward()
+        in train mode additionally sends every pool-free features.bn_bf16_trainable BatchNorm of
+        the blocks (a bf16 activation, fp32 parameters, batch statistics, no running-statistics
+        update pending: the 19 of ResNet-18, 16 in blocks and 3 downsample), with the residual add
+        and ReLU that follow it, through the differentiable op torch.ops.mcgmil.bn_act_bf16: the
+        fused bf16 HIP forward and the HIP backward of include/mcgmil_bn_grad_bf16.h instead of
+        torch's batch_norm / add / relu kernels and their backward (timings in DESIGN.md §4). It
+        does not depend on MCGMIL_CONV_GRAD. The stem's bn1 / relu / maxpool, the stem convolution
+        and the head stay as they are. A method of its own, so that enable_bf16_backbone_training
+        keeps its signature. Off by default; enable_bf16_backbone_training(False) switches it off;
+        returns self."""
+        self._bf16_norm_training = bool(flag)
         return self
 
     def _live_head(self):
@@ -346,7 +365,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                     features.native_stem_training(self._stem_training), \
                     features.native_stem_conv_training(self._stem_conv_training):
                 if self._bf16_backbone_training:
-                    with torch.autocast("cuda", torch.bfloat16), features.native_conv_bf16_training():
+                    with torch.autocast("cuda", torch.bfloat16), features.native_conv_bf16_training(), \
+                            features.native_norm_bf16_training(self._bf16_norm_training):
                         H = self.extract_features(x)
                 else:
                     H = self.extract_features(x)
