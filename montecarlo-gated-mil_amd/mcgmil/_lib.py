@@ -74,6 +74,10 @@ CONV_GRAD_BF16_EXPORTED = ("mcgmil_conv_grad_bf16_args_size", "mcgmil_conv_wgrad
 BN_GRAD_BF16_EXPORTED = ("mcgmil_bn_grad_bf16_args_size", "mcgmil_bn_grad_workspace_size_bf16",
                          "mcgmil_batchnorm_act_backward_bf16")
 
+# include/mcgmil_pool_grad_bf16.h (the stem's bf16 BatchNorm/ReLU/max-pool training op; additive as well)
+POOL_GRAD_BF16_EXPORTED = ("mcgmil_batchnorm_pool_train_bf16", "mcgmil_bn_pool_grad_bf16_args_size",
+                           "mcgmil_bn_pool_grad_workspace_size_bf16", "mcgmil_batchnorm_pool_backward_bf16")
+
 _vp = ctypes.c_void_p
 
 
@@ -200,6 +204,12 @@ class BnPoolGradArgs(ctypes.Structure):
         ("dz", _vp), ("dgamma", _vp), ("dbeta", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int64),
     ]
+
+
+class BnPoolGradBf16Args(ctypes.Structure):
+    """Mirror of struct mcgmil_bn_pool_grad_bf16_args (include/mcgmil_pool_grad_bf16.h): the fields of
+    mcgmil_bn_pool_grad_args, with bf16 z / dy / dz."""
+    _fields_ = list(BnPoolGradArgs._fields_)
 
 
 BN_POOL_GRAD_PART_ELEMS = 32768    # MCGMIL_BN_POOL_GRAD_PART_ELEMS
@@ -403,6 +413,17 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_bn_pool_grad_args_size() != ctypes.sizeof(BnPoolGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_pool_grad_args)={L.mcgmil_bn_pool_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(BnPoolGradArgs)} bytes")
+    ppb = ctypes.POINTER(BnPoolGradBf16Args)
+    L.mcgmil_batchnorm_pool_train_bf16.argtypes = [pb, _vp, _vp]
+    L.mcgmil_batchnorm_pool_train_bf16.restype = ctypes.c_int
+    L.mcgmil_bn_pool_grad_bf16_args_size.restype = ctypes.c_size_t
+    L.mcgmil_bn_pool_grad_workspace_size_bf16.argtypes = [ppb, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_bn_pool_grad_workspace_size_bf16.restype = ctypes.c_int
+    L.mcgmil_batchnorm_pool_backward_bf16.argtypes = [ppb, _vp]
+    L.mcgmil_batchnorm_pool_backward_bf16.restype = ctypes.c_int
+    if L.mcgmil_bn_pool_grad_bf16_args_size() != ctypes.sizeof(BnPoolGradBf16Args):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_bn_pool_grad_bf16_args)={L.mcgmil_bn_pool_grad_bf16_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(BnPoolGradBf16Args)} bytes")
     ps = ctypes.POINTER(StemArgs)
     L.mcgmil_stem_args_size.restype = ctypes.c_size_t
     for name in ("mcgmil_stem_packed_size", "mcgmil_stem_workspace_size"):

@@ -59,6 +59,12 @@ Inside `native_norm_bf16_training()` (enable_bf16_norm_training()) `bn_act` send
 pool-free `bn_bf16_trainable` BatchNorm (+ residual add) (+ ReLU) that autograd tracks to
 torch.ops.mcgmil.bn_act_bf16: `batchnorm_act_stats_bf16` is its forward (mcgmil_batchnorm_act in
 bf16), `batchnorm_act_backward_bf16` its HIP backward (include/mcgmil_bn_grad_bf16.h).
+Inside `native_stem_bf16_training()` (enable_bf16_stem_training()) `bn_act` sends the stem's
+`bn_pool_bf16_trainable` BatchNorm + ReLU + max-pool that autograd tracks (a bf16 activation) to
+torch.ops.mcgmil.bn_pool_bf16: `batchnorm_pool_stats_bf16` is its forward
+(mcgmil_batchnorm_pool_train_bf16: batchnorm_act's pooled bf16 output bit for bit, plus the argmax
+codes taken on the unrounded fp32 value), `batchnorm_pool_backward_bf16` its HIP backward
+(include/mcgmil_pool_grad_bf16.h).
 """
 import contextlib
 import ctypes
@@ -1464,6 +1470,139 @@ def bn_pool_f32_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, pool: nn.Max
     return torch.ops.mcgmil.bn_pool_f32(x, bn.weight, bn.bias, float(bn.eps), bool(relu), k, stride, pad)[0]
 
 
+# ---------------------------------------------------------------- fused bf16 stem BatchNorm / pool backward
+_native_stem_bf16_training = False
+
+
+@contextlib.contextmanager
+def native_stem_bf16_training(flag: bool = True):
+    """Inside this context `bn_act` sends a `bn_pool_bf16_trainable` BatchNorm (+ ReLU) + max-pool
+    that autograd tracks (a bf16 activation: the ResNet stem's bn1 / relu / maxpool under
+    torch.autocast("cuda", torch.bfloat16)) to the differentiable op torch.ops.mcgmil.bn_pool_bf16
+    (the fused bf16 HIP forward that also records the pool's argmax codes, and the HIP backward of
+    include/mcgmil_pool_grad_bf16.h). Off outside it: the opt-in of
+    MultiHeadGatedAttentionMIL.enable_bf16_stem_training()."""
+    global _native_stem_bf16_training
+    before, _native_stem_bf16_training = _native_stem_bf16_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_stem_bf16_training = before
+
+
+def bn_pool_bf16_untrainable_reason(x: torch.Tensor, bn: nn.Module, pool: nn.Module) -> Optional[str]:
+    """Why `bn_pool_bf16_trainable` refuses (x, bn, pool), or None when it holds: the pool's clause
+    of `bn_pool_untrainable_reason`, then the clauses of `bn_bf16_untrainable_reason` (the device
+    last)."""
+    pp = _pool_params(pool)
+    if pp is None or not _pool_grad_geometry(*pp):
+        return "pool: a square floor-mode nn.MaxPool2d, dilation 1, kernel 2 or 3, 1 <= stride <= kernel, pad <= kernel / 2"
+    if x.dim() == 4 and min((x.shape[2] + 2 * pp[2] - pp[0]) // pp[1], (x.shape[3] + 2 * pp[2] - pp[0]) // pp[1]) < 0:
+        return "pool: the window is larger than the padded input"
+    return bn_bf16_untrainable_reason(x, bn)
+
+
+def bn_pool_bf16_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, pool: nn.Module) -> bool:
+    """A BatchNorm (+ ReLU) + max-pool whose forward AND backward run on the fused bf16 HIP kernels
+    of include/mcgmil_pool_grad_bf16.h: `bn_bf16_trainable(x, bn)` and the pool of
+    `bn_pool_trainable`. `bn_pool_bf16_untrainable_reason` names the clause that fails."""
+    return bn_pool_bf16_untrainable_reason(x, bn, pool) is None
+
+
+def batchnorm_pool_stats_bf16(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+                              eps: float, relu: bool, k: int, stride: int, pad: int):
+    """(y bf16, mean [C] fp32, invstd [C] fp32, argmax) of max_pool2d(relu?(batch_norm(z)), k, stride,
+    pad) on the batch statistics of z (bf16, channels-last; weight and bias fp32):
+    mcgmil_batchnorm_pool_train_bf16. y is bitwise batchnorm_act(..., pool=...) on the bf16 z; argmax
+    is a channels-last uint8 [N, C, PH, PW] tensor of window codes kh * k + kw taken on the unrounded
+    fp32 activated value (255: the ReLU zeroes that gradient). What batchnorm_pool_backward_bf16
+    needs."""
+    _check_rows_c_bf16("batchnorm_pool_stats_bf16", z)
+    if not _pool_grad_geometry(k, stride, pad):
+        raise ValueError("batchnorm_pool_stats_bf16 needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
+                         "0 <= pad <= kernel / 2")
+    L = _lib.load()
+    dev = z.device
+    N, C, H, W = z.shape
+    PH, PW = _pooled_hw(H, W, k, stride, pad)
+    if PH < 1 or PW < 1:
+        raise ValueError("batchnorm_pool_stats_bf16: the pooling window is larger than the padded input")
+    _check_per_channel("batchnorm_pool_stats_bf16", C, dev, weight=weight, bias=bias)
+    y = torch.empty((N, C, PH, PW), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
+    argmax = torch.empty((N, C, PH, PW), dtype=torch.uint8, device=dev, memory_format=torch.channels_last)
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    invstd = torch.empty(C, dtype=torch.float32, device=dev)
+    a = _lib.BnArgs()
+    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_BF16
+    a.batch, a.height, a.width = N, H, W
+    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.x, a.y = p(z), p(y)
+    a.gamma, a.beta = p(weight), p(bias)
+    a.eps, a.relu = float(eps), int(bool(relu))
+    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
+    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_pool_train_bf16(ctypes.byref(a), p(argmax), stream),
+               "mcgmil_batchnorm_pool_train_bf16")
+    return y, mean, invstd, argmax
+
+
+def batchnorm_pool_backward_bf16(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor,
+                                 weight: Optional[torch.Tensor], mean: torch.Tensor, invstd: torch.Tensor,
+                                 k: int, stride: int, pad: int, need_dz: bool = True, need_dw: bool = True):
+    """(dz bf16, dweight fp32, dbias fp32), None where not needed, of batchnorm_pool_stats_bf16 given
+    dy (mcgmil_batchnorm_pool_backward_bf16, include/mcgmil_pool_grad_bf16.h). argmax holds the
+    forward's window codes; dy is channels-last bf16 [N, C, PH, PW]."""
+    _check_rows_c_bf16("batchnorm_pool_backward_bf16", z)
+    if not _pool_grad_geometry(k, stride, pad):
+        raise ValueError("batchnorm_pool_backward_bf16 needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
+                         "0 <= pad <= kernel / 2")
+    dev = z.device
+    N, C, H, W = z.shape
+    PH, PW = _pooled_hw(H, W, k, stride, pad)
+    for name, t, dt in (("argmax", argmax, torch.uint8), ("dy", dy, torch.bfloat16)):
+        if tuple(t.shape) != (N, C, PH, PW) or t.dtype != dt or t.device != dev or \
+                not t.is_contiguous(memory_format=torch.channels_last):
+            raise ValueError(f"batchnorm_pool_backward_bf16: {name} must be a channels-last {dt} {(N, C, PH, PW)} "
+                             "tensor on z's device")
+    if not (need_dz or need_dw):
+        return None, None, None
+    L = _lib.load()
+    _check_per_channel("batchnorm_pool_backward_bf16", C, dev, weight=weight, mean=mean, invstd=invstd)
+    dz = torch.empty_like(z, memory_format=torch.channels_last) if need_dz else None
+    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    a = _lib.BnPoolGradBf16Args()
+    a.batch, a.height, a.width, a.channels = N, H, W, C
+    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
+    a.pooled_height, a.pooled_width = PH, PW
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    a.z, a.argmax, a.dy = p(z), p(argmax), p(dy)
+    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
+    a.dz, a.dgamma, a.dbeta = p(dz), p(dw), p(db)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_bn_pool_grad_workspace_size_bf16(ctypes.byref(a), ctypes.byref(n)),
+               "mcgmil_bn_pool_grad_workspace_size_bf16")
+    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
+    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(L.mcgmil_batchnorm_pool_backward_bf16(ctypes.byref(a), stream), "mcgmil_batchnorm_pool_backward_bf16")
+    return dz, dw, db
+
+
+def bn_pool_bf16_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, pool: nn.MaxPool2d) -> torch.Tensor:
+    """pool(relu?(bn(x))) through the differentiable op torch.ops.mcgmil.bn_pool_bf16
+    (mcgmil.library); the activation is made channels-last first if it is not."""
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    k, stride, pad = _pool_params(pool)
+    x = x.contiguous(memory_format=torch.channels_last)
+    return torch.ops.mcgmil.bn_pool_bf16(x, bn.weight, bn.bias, float(bn.eps), bool(relu), k, stride, pad)[0]
+
+
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
            residual: Optional[torch.Tensor] = None, pool: Optional[nn.Module] = None) -> torch.Tensor:
     """The backbone's `pool?(relu?(bn(x) [+ residual]))`: fused on the GPU when `fusable`, else
@@ -1471,7 +1610,9 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
     native_norm_training() a pool-free `bn_trainable` layer under autograd goes to the
     differentiable fused op instead of the torch layers; inside native_stem_training() a
     residual-free `bn_pool_trainable` layer with a pool does; inside native_norm_bf16_training()
-    a pool-free `bn_bf16_trainable` layer (a bf16 activation) goes to the bf16 fused op."""
+    a pool-free `bn_bf16_trainable` layer (a bf16 activation) goes to the bf16 fused op; inside
+    native_stem_bf16_training() a residual-free `bn_pool_bf16_trainable` layer with a pool (a bf16
+    activation) goes to the bf16 fused pool op."""
     tracked = torch.is_grad_enabled() and isinstance(bn, nn.BatchNorm2d) and \
         (x.requires_grad or any(p.requires_grad for p in bn.parameters()))
     if _native_stem_training and pool is not None and residual is None and tracked and bn_pool_trainable(x, bn, pool):
@@ -1480,6 +1621,9 @@ def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
         return bn_act_f32_op(bn, x, relu, residual)
     if _native_norm_bf16_training and pool is None and tracked and bn_bf16_trainable(x, bn, residual):
         return bn_act_bf16_op(bn, x, relu, residual)
+    if _native_stem_bf16_training and pool is not None and residual is None and tracked and \
+            bn_pool_bf16_trainable(x, bn, pool):
+        return bn_pool_bf16_op(bn, x, relu, pool)
     if fusable(x, bn, residual):
         if pool is None or (residual is None and _pool_params(pool) is not None):
             return batchnorm_act(x, bn, relu, residual, pool)

@@ -29,6 +29,10 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.bn_act_bf16_backward(x, y, dy, weight?, mean, invstd, relu, need_dx, need_dres,
                                           need_dw) -> (dx, dres, dweight, dbias)
 
+    torch.ops.mcgmil.bn_pool_bf16(z, weight?, bias?, eps, relu, k, stride, pad) -> (y, mean, invstd, argmax)
+    torch.ops.mcgmil.bn_pool_bf16_backward(z, argmax, dy, weight?, mean, invstd, k, stride, pad, need_dz,
+                                           need_dw) -> (dz, dweight, dbias)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -83,6 +87,15 @@ with MCGMIL_BF16). Its formula saves the same tensors and calls bn_act_bf16_back
 dx and dres come back bf16, dweight and dbias fp32. Without ReLU the residual's gradient is dy
 itself; gradients flowing into mean and invstd are ignored.
 
+bn_pool_bf16 is bn_pool_f32 in mixed precision: z and y bf16, weight and bias the fp32 master
+parameters, mean and invstd fp32 (features.batchnorm_pool_stats_bf16:
+mcgmil_batchnorm_pool_train_bf16). The codes name the largest UNROUNDED fp32 value of the window
+(where two taps round to the same bf16 value torch's autocast layers name the first of them
+instead; both are subgradients of the same y). Its formula saves the same tensors, z, argmax, mean,
+invstd and weight alone, and calls bn_pool_bf16_backward (features.batchnorm_pool_backward_bf16,
+include/mcgmil_pool_grad_bf16.h), which has no formula itself: dz comes back bf16, dweight and
+dbias fp32.
+
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
@@ -98,7 +111,7 @@ from . import features, ops
 __all__ = ["mcdo_forward", "mcdo_forward_stats", "mcdo_backward", "conv2d_f32", "conv2d_f32_backward",
            "bn_act_f32", "bn_act_f32_backward", "bn_pool_f32", "bn_pool_f32_backward",
            "stem_conv_f32", "stem_conv_f32_backward", "conv2d_bf16", "conv2d_bf16_backward",
-           "bn_act_bf16", "bn_act_bf16_backward"]
+           "bn_act_bf16", "bn_act_bf16_backward", "bn_pool_bf16", "bn_pool_bf16_backward"]
 
 
 def _head(Wv, bv, Wu, bu, wa, ba, wk) -> ops.HeadTensors:
@@ -448,6 +461,61 @@ def _bn_pool_backward(ctx, dy, dmean, dinvstd, dargmax):
 
 
 bn_pool_f32.register_autograd(_bn_pool_backward, setup_context=_bn_pool_setup_context)
+
+
+@torch.library.custom_op("mcgmil::bn_pool_bf16", mutates_args=())
+def bn_pool_bf16(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+                 relu: bool, k: int, stride: int, pad: int
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
+        return features.batchnorm_pool_stats_bf16(_channels_last(z), f(weight), f(bias), eps, relu, k, stride, pad)
+
+
+@bn_pool_bf16.register_fake
+def _bn_pool_bf16_fake(z, weight, bias, eps, relu, k, stride, pad):
+    shape = _pooled_shape(z, k, stride, pad)
+    y = torch.empty(shape, dtype=torch.bfloat16, device=z.device, memory_format=torch.channels_last)
+    argmax = torch.empty(shape, dtype=torch.uint8, device=z.device, memory_format=torch.channels_last)
+    return (y, z.new_empty((z.shape[1],), dtype=torch.float32), z.new_empty((z.shape[1],), dtype=torch.float32),
+            argmax)
+
+
+@torch.library.custom_op("mcgmil::bn_pool_bf16_backward", mutates_args=())
+def bn_pool_bf16_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                          mean: torch.Tensor, invstd: torch.Tensor, k: int, stride: int, pad: int, need_dz: bool,
+                          need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    with torch.no_grad():
+        dz, dw, db = features.batchnorm_pool_backward_bf16(
+            _channels_last(z), _channels_last(argmax), _channels_last(dy.to(torch.bfloat16)),
+            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
+            invstd.detach().contiguous(), k, stride, pad, need_dz, need_dw)
+    e = lambda t, like: like.new_empty((0,)) if t is None else t  # noqa: E731
+    return e(dz, z), e(dw, mean), e(db, mean)
+
+
+@bn_pool_bf16_backward.register_fake
+def _bn_pool_bf16_backward_fake(z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
+    dz = torch.empty(z.shape, dtype=torch.bfloat16, device=z.device, memory_format=torch.channels_last) \
+        if need_dz else z.new_empty((0,))
+    vec = lambda: mean.new_empty((z.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+    return dz, vec(), vec()
+
+
+def _bn_pool_bf16_backward(ctx, dy, dmean, dinvstd, dargmax):
+    # as _bn_pool_backward: the saved tensors are z, the codes, mean, invstd and weight alone
+    if dy is None:
+        return (None,) * 8
+    z, argmax, mean, invstd, *rest = ctx.saved_tensors
+    weight = rest[0] if ctx.has_weight else None
+    need = ctx.needs_input_grad
+    need_dz, need_dw = need[0], need[1] or need[2]
+    dz, dw, db = torch.ops.mcgmil.bn_pool_bf16_backward(z, argmax, dy, weight, mean, invstd, *ctx.geometry,
+                                                        need_dz, need_dw)
+    return (dz if need_dz else None, dw if need[1] else None, db if need[2] else None) + (None,) * 5
+
+
+bn_pool_bf16.register_autograd(_bn_pool_bf16_backward, setup_context=_bn_pool_setup_context)
 
 
 def _stem_conv_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):

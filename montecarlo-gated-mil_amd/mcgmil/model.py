@@ -108,6 +108,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._stem_conv_training = False
         self._bf16_backbone_training = False
         self._bf16_norm_training = False
+        self._bf16_stem_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -289,12 +290,14 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         the forward kernel again as the stride-1 data gradient; default: aten.convolution_backward
         on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
         by layer, so the stem convolution, BatchNorm, ReLU and the pools are the torch layers under
-        autocast, unless enable_bf16_norm_training() is on as well. The head stays fp32. Eval mode,
-        no_grad and the default are unchanged. Off by default; switching it off switches
-        enable_bf16_norm_training off too; returns self."""
+        autocast, unless enable_bf16_norm_training() (the blocks' BatchNorms) or
+        enable_bf16_stem_training() (the stem's bn1 / relu / maxpool) is on as well. The head stays
+        fp32. Eval mode, no_grad and the default are unchanged. Off by default; switching it off
+        switches enable_bf16_norm_training and enable_bf16_stem_training off too; returns self."""
         self._bf16_backbone_training = bool(flag)
         if not flag:
             self._bf16_norm_training = False
+            self._bf16_stem_training = False
         return self
 
     def enable_bf16_norm_training(self, flag=True):
@@ -305,11 +308,28 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         and ReLU that follow it, through the differentiable op torch.ops.mcgmil.bn_act_bf16: the
         fused bf16 HIP forward and the HIP backward of include/mcgmil_bn_grad_bf16.h instead of
         torch's batch_norm / add / relu kernels and their backward (timings in DESIGN.md §4). It
-        does not depend on MCGMIL_CONV_GRAD. The stem's bn1 / relu / maxpool, the stem convolution
-        and the head stay as they are. A method of its own, so that enable_bf16_backbone_training
-        keeps its signature. Off by default; enable_bf16_backbone_training(False) switches it off;
-        returns self."""
+        does not depend on MCGMIL_CONV_GRAD. The stem's bn1 / relu / maxpool (unless
+        enable_bf16_stem_training() is on), the stem convolution and the head stay as they are. A
+        method of its own, so that enable_bf16_backbone_training keeps its signature. Off by
+        default; enable_bf16_backbone_training(False) switches it off; returns self."""
         self._bf16_norm_training = bool(flag)
+        return self
+
+    def enable_bf16_stem_training(self, flag=True):
+        """On top of enable_bf16_backbone_training(), and in effect only while that is on: forward()
+        in train mode additionally sends the stem's bn1 / relu / maxpool, when
+        features.bn_pool_bf16_trainable (a bf16 activation, fp32 parameters, batch statistics, no
+        running-statistics update pending, a 2- or 3-wide pool), through the differentiable op
+        torch.ops.mcgmil.bn_pool_bf16: the fused bf16 HIP forward, which keeps one byte per pooled
+        element instead of a full-size bf16 BatchNorm/ReLU output and the pool's int64 indices, and
+        the HIP backward of include/mcgmil_pool_grad_bf16.h, instead of torch's batch_norm / relu /
+        max_pool2d kernels under autocast and their backward (timings in DESIGN.md §4). Where two
+        taps of a window round to the same bf16 value the gradient goes to the one whose unrounded
+        value is larger, not to the first as under torch (include/mcgmil_pool_grad_bf16.h). It
+        depends on neither enable_bf16_norm_training() nor MCGMIL_CONV_GRAD. The stem convolution
+        stays the torch layer under autocast. A method of its own, so that the existing signatures
+        stay. Off by default; enable_bf16_backbone_training(False) switches it off; returns self."""
+        self._bf16_stem_training = bool(flag)
         return self
 
     def _live_head(self):
@@ -366,7 +386,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                     features.native_stem_conv_training(self._stem_conv_training):
                 if self._bf16_backbone_training:
                     with torch.autocast("cuda", torch.bfloat16), features.native_conv_bf16_training(), \
-                            features.native_norm_bf16_training(self._bf16_norm_training):
+                            features.native_norm_bf16_training(self._bf16_norm_training), \
+                            features.native_stem_bf16_training(self._bf16_stem_training):
                         H = self.extract_features(x)
                 else:
                     H = self.extract_features(x)
