@@ -65,6 +65,15 @@ torch.ops.mcgmil.bn_pool_bf16: `batchnorm_pool_stats_bf16` is its forward
 (mcgmil_batchnorm_pool_train_bf16: batchnorm_act's pooled bf16 output bit for bit, plus the argmax
 codes taken on the unrounded fp32 value), `batchnorm_pool_backward_bf16` its HIP backward
 (include/mcgmil_pool_grad_bf16.h).
+
+How the bindings are laid out: every operation is bound once, with the dtype as a parameter, and
+the public fp32 / bf16 names are thin wrappers over it. `_ptr`, `_stream` and `_workspace` do the
+marshalling; `_conv_args` fills mcgmil_conv_args (also as the `fwd` of the gradient structs) and
+`_bn_args` mcgmil_bn_args; `_conv_refusal` is the one walk over the clauses of the native
+convolutions' domains (the six conv predicates differ in its keywords alone), `_bn_refusal` and
+`_bn_pool_refusal` the same for the BatchNorm training ops; `_wgrad`, `_bn_stats`,
+`_bn_act_backward` and `_bn_pool_backward` are the shared bodies, `_TWIN` what differs between an
+fp32 op and its bf16 twin. tests/test_features_bindings_host.py pins what reaches the C ABI.
 """
 import contextlib
 import ctypes
@@ -77,6 +86,54 @@ import torch.nn as nn
 from . import _lib
 
 _DT = {torch.float32: _lib.MCGMIL_F32, torch.bfloat16: _lib.MCGMIL_BF16}
+_CL = torch.channels_last
+
+
+# ---------------------------------------------------------------- marshalling
+def _ptr(t: Optional[torch.Tensor]) -> Optional[ctypes.c_void_p]:
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(dev) -> ctypes.c_void_p:
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _workspace(size_fn, what: str, args, dev, optional: bool = False) -> None:
+    """Ask size_fn (the entry point named `what`) for the bytes `args` needs and point
+    args.workspace at that many from the caching allocator. The tensor lives as long as `args`:
+    until after the launches, and its memory is freed stream-ordered. optional: a size of 0 leaves
+    args.workspace NULL."""
+    n = ctypes.c_size_t()
+    _lib.check(size_fn(ctypes.byref(args), ctypes.byref(n)), what)
+    if n.value or not optional:
+        args._workspace_tensor = ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        args.workspace, args.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value
+
+
+def _square(v):
+    return v if isinstance(v, int) else (v[0] if len(set(v)) == 1 else None)
+
+
+def _out_hw(H: int, W: int, kh: int, kw: int, stride: int, pad: int):
+    """The output extent of a convolution or pooling window."""
+    return (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+
+
+def _use_batch(bn: nn.BatchNorm2d) -> bool:
+    return bn.training or bn.running_mean is None or bn.running_var is None
+
+
+# what differs between an fp32 training op and its bf16 twin: the suffix of the wrapper's and the
+# entry points' names, the word for the dtype, the args structs of the two backwards
+class _Twin(NamedTuple):
+    suffix: str
+    word: str
+    bn_grad_args: type
+    bn_pool_grad_args: type
+
+
+_TWIN = {torch.float32: _Twin("", "fp32", _lib.BnGradArgs, _lib.BnPoolGradArgs),
+         torch.bfloat16: _Twin("_bf16", "bf16", _lib.BnGradBf16Args, _lib.BnPoolGradBf16Args)}
 
 
 def enabled() -> bool:
@@ -105,42 +162,122 @@ def conv_enabled() -> bool:
     return os.environ.get("MCGMIL_NATIVE_CONV", "1") != "0"
 
 
-def _square(v):
-    return v if isinstance(v, int) else (v[0] if len(set(v)) == 1 else None)
+def conv32_enabled() -> bool:
+    """MCGMIL_NATIVE_CONV32=0 keeps fp32 convolutions on the torch layers (MIOpen)."""
+    return os.environ.get("MCGMIL_NATIVE_CONV32", "1") != "0" and conv_enabled()
+
+
+# ---------------------------------------------------------------- the native convolutions' domains
+def _conv_refusal(conv: nn.Module, t: torch.Tensor, *, fp32: bool, weights: Optional[tuple], autocast: str,
+                  in_channels: str, strides: Optional[tuple] = (1, 2), pad_below_kernel: bool = True,
+                  out_max: Optional[int] = None, of_dy: bool = False, nonempty: bool = True,
+                  channels_last: bool = True, pixels: Optional[str] = "positive", below_2gib: bool = False,
+                  max_hw: Optional[int] = None, autograd: bool = False) -> Optional[str]:
+    """Why `conv` on the activation `t` is outside a native convolution's domain: the first clause
+    that fails, or None. Every predicate below is this walk with its own keywords:
+      fp32          an fp32 activation behind MCGMIL_NATIVE_CONV32, else a bf16 one behind MCGMIL_NATIVE_CONV
+      weights       the weight dtypes taken (None: any)
+      autocast      "refuse" it, "ignore" it (never asked), or "bf16": autocast to bf16 stands in for a bf16 weight
+      in_channels   "64" / "16": a multiple of it, "1..4", or "16 or gather": % 16 or kh * kw * in <= 1024
+      strides       the square strides taken (None: any)
+      out_max       the largest out_channels (None: no limit); always a multiple of 64
+      of_dy         t is dY, [batch, out_channels, OH, OW], not x
+      pixels        "positive": 1 <= OH, OW and batch * OH * OW < 2^31 - 256; "any": the product alone; None
+      below_2gib, max_hw   the bf16 kernels' limits on t: numel * 2 < 2^31, height and width <= max_hw
+      autograd      refuse what autograd tracks (the inference predicates)"""
+    if not (conv32_enabled() if fp32 else conv_enabled()):
+        return "the native fp32 convolutions are switched off (MCGMIL_NATIVE_CONV32 / MCGMIL_NATIVE_CONV)" if fp32 \
+            else "the native convolutions are switched off (MCGMIL_NATIVE_CONV)"
+    if not isinstance(conv, nn.Conv2d):
+        return "not an nn.Conv2d"
+    if not (t.is_cuda and t.dim() == 4):
+        return "the activation is not a 4-d CUDA tensor"
+    if fp32:
+        if t.dtype != torch.float32 or (weights is not None and conv.weight.dtype not in weights):
+            return "the activation and the weight must be fp32"
+    else:
+        if t.dtype != torch.bfloat16:
+            return "the activation must be bf16"
+        if conv.weight.dtype not in weights and not (
+                autocast == "bf16" and torch.is_autocast_enabled("cuda") and
+                torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return "the weight must be fp32 or bf16"
+    if autocast == "refuse" and torch.is_autocast_enabled("cuda"):
+        return "autocast is enabled"
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return "only a bias-free groups=1 zero-padded convolution"
+    stride = _square(conv.stride)
+    if _square(conv.dilation) != 1 or (stride is None if strides is None else stride not in strides) or \
+            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
+        return "dilation 1, a square stride of 1 or 2 and a square integer padding"
+    kh, kw = conv.kernel_size
+    pad = conv.padding[0]
+    if not (1 <= kh <= 7 and 1 <= kw <= 7) or (pad_below_kernel and pad >= min(kh, kw)):
+        return "kernel 1..7 per axis and pad < min(kh, kw)"
+    cin = conv.in_channels
+    if in_channels == "1..4":
+        if not 1 <= cin <= 4:
+            return "in_channels must be in 1..4"
+    elif in_channels == "16 or gather":
+        if cin % 16 and kh * kw * cin > 1024:
+            return "in_channels must be a multiple of 16, or kh * kw * in_channels at most 1024"
+    elif cin % int(in_channels):
+        return f"in_channels must be a multiple of {in_channels}"
+    if conv.out_channels % 64 or (out_max is not None and conv.out_channels > out_max):
+        return "out_channels must be a multiple of 64" + ("" if out_max is None else f" (at most {out_max})")
+    if t.shape[1] != (conv.out_channels if of_dy else cin):
+        return "the activation's channels are not the convolution's in_channels"
+    if (nonempty and t.numel() == 0) or (channels_last and not t.is_contiguous(memory_format=_CL)):
+        return "the activation must be non-empty and channels-last"
+    if pixels is not None:
+        oh, ow = _out_hw(t.shape[2], t.shape[3], kh, kw, stride, pad)
+        if (pixels == "positive" and (oh < 1 or ow < 1)) or t.shape[0] * oh * ow >= 2 ** 31 - 256:
+            return "batch * OH * OW must be in 1 .. 2^31 - 257"
+    if (below_2gib and t.numel() * 2 >= 2 ** 31) or (max_hw is not None and max(t.shape[2], t.shape[3]) > max_hw):
+        return "the activation must be smaller than 2 GiB, height and width at most 16383"
+    if autograd and torch.is_grad_enabled() and (t.requires_grad or conv.weight.requires_grad):
+        return "autograd tracks the activation or the weight"
+    return None
+
+
+_CONV_FUSABLE = dict(fp32=False, weights=(torch.bfloat16,), autocast="bf16", in_channels="64", strides=None,
+                     pad_below_kernel=False, nonempty=False, pixels=None, below_2gib=True, autograd=True)
+_CONV32_FUSABLE = dict(fp32=True, weights=None, autocast="refuse", in_channels="16 or gather", strides=None,
+                       pad_below_kernel=False, nonempty=False, pixels="any", autograd=True)
+_CONV32_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="16")
+_STEM_CONV_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="1..4", out_max=4096)
+_CONV_BF16_TRAINABLE = dict(fp32=False, weights=(torch.float32, torch.bfloat16), autocast="ignore", in_channels="64",
+                            below_2gib=True, max_hw=16383)
+_DGRAD_DIRECT = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="16", of_dy=True,
+                     channels_last=False, pixels=None)
 
 
 def conv_fusable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     """A CUDA channels-last activation that torch would convolve in bf16 (bf16 input, or autocast
     to bf16), with a convolution the kernel implements, and no autograd."""
-    if not (conv_enabled() and isinstance(conv, nn.Conv2d) and x.is_cuda and x.dim() == 4):
-        return False
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return False
-    if _square(conv.dilation) != 1 or _square(conv.stride) is None or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return False
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7):
-        return False
-    if conv.in_channels % 64 or conv.out_channels % 64 or x.shape[1] != conv.in_channels:
-        return False
-    bf16 = x.dtype == torch.bfloat16 and (
-        conv.weight.dtype == torch.bfloat16 or
-        (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16))
-    if not bf16 or not x.is_contiguous(memory_format=torch.channels_last):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
-        return False
-    return x.numel() * 2 < 2 ** 31
+    return _conv_refusal(conv, x, **_CONV_FUSABLE) is None
 
 
-def _conv_args(conv: nn.Conv2d, x: torch.Tensor):
+def _conv_args(conv: nn.Conv2d, x) -> "_lib.ConvArgs":
+    """mcgmil_conv_args with the geometry of conv on x (a tensor, or the shape of one)."""
     a = _lib.ConvArgs()
-    a.batch, _, a.height, a.width = x.shape
+    a.batch, _, a.height, a.width = x.shape if isinstance(x, torch.Tensor) else (int(v) for v in x)
     a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
     a.kernel_h, a.kernel_w = conv.kernel_size
     a.stride, a.pad = _square(conv.stride), _square(conv.padding)
     return a
+
+
+def _conv_out_shape(a: "_lib.ConvArgs") -> tuple:
+    return (a.batch, a.out_channels) + _out_hw(a.height, a.width, a.kernel_h, a.kernel_w, a.stride, a.pad)
+
+
+def _set_in_ab(a: "_lib.ConvArgs", in_ab: Optional[torch.Tensor], in_relu: bool, dev) -> None:
+    if in_ab is not None:
+        if in_ab.shape != (2, a.in_channels) or in_ab.dtype != torch.float32 or \
+                in_ab.device != dev or not in_ab.is_contiguous():
+            raise ValueError("in_ab must be a contiguous fp32 [2, in_channels] tensor on x's device")
+        a.in_ab, a.in_relu = _ptr(in_ab), int(bool(in_relu))
 
 
 def packed_conv_weight(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
@@ -156,11 +293,8 @@ def packed_conv_weight(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
         w = w.to(device=x.device, dtype=torch.float32)
     w = w.contiguous()
     packed = torch.empty(w.numel(), dtype=torch.bfloat16, device=x.device)
-    a = _conv_args(conv, x)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_pack_conv_weights(ctypes.byref(a), ctypes.c_void_p(w.data_ptr()),
-                                          _DT[w.dtype], ctypes.c_void_p(packed.data_ptr()), stream),
-               "mcgmil_pack_conv_weights")
+    _lib.check(L.mcgmil_pack_conv_weights(ctypes.byref(_conv_args(conv, x)), _ptr(w), _DT[w.dtype], _ptr(packed),
+                                          _stream(x.device)), "mcgmil_pack_conv_weights")
     conv._mcgmil_packed = (key, packed)
     return packed
 
@@ -207,70 +341,31 @@ def _conv2d(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
     """conv2d without its predicate: for callers that have checked the domain themselves (conv2d
     after conv_fusable, conv2d_bf16 after conv_bf16_trainable)."""
     L = _lib.load()
+    dev = x.device
     a = _conv_args(conv, x)
     a.flags = int(flags)
-    if in_ab is not None:
-        if in_ab.shape != (2, a.in_channels) or in_ab.dtype != torch.float32 or \
-                in_ab.device != x.device or not in_ab.is_contiguous():
-            raise ValueError("in_ab must be a contiguous fp32 [2, in_channels] tensor on x's device")
-        a.in_ab, a.in_relu = ctypes.c_void_p(in_ab.data_ptr()), int(bool(in_relu))
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    y = torch.empty((a.batch, a.out_channels, oh, ow), dtype=torch.bfloat16, device=x.device,
-                    memory_format=torch.channels_last)
+    _set_in_ab(a, in_ab, in_relu, dev)
+    y = torch.empty(_conv_out_shape(a), dtype=torch.bfloat16, device=dev, memory_format=_CL)
     w = packed_conv_weight(conv, x)
-    a.x, a.w, a.y = (ctypes.c_void_p(t.data_ptr()) for t in (x, w, y))
-    ws = None
+    a.x, a.w, a.y = _ptr(x), _ptr(w), _ptr(y)
     if split_enabled():
-        nb = ctypes.c_size_t()
-        _lib.check(L.mcgmil_conv_workspace_size(ctypes.byref(a), ctypes.byref(nb)), "mcgmil_conv_workspace_size")
-        if nb.value:
-            ws = torch.empty(nb.value, dtype=torch.uint8, device=x.device)   # freed after the launch,
-            a.workspace, a.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), nb.value   # stream-ordered
+        _workspace(L.mcgmil_conv_workspace_size, "mcgmil_conv_workspace_size", a, dev, optional=True)
     part = None
     if stats:
         n = ctypes.c_int32()
         _lib.check(L.mcgmil_conv_stats_parts(ctypes.byref(a), ctypes.byref(n)), "mcgmil_conv_stats_parts")
         if n.value > 0:          # 0: this layer's kernel emits no statistics
-            part = torch.empty((n.value, 3, a.out_channels), dtype=torch.float32, device=x.device)
-            a.stats = ctypes.c_void_p(part.data_ptr())
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_conv2d(ctypes.byref(a), stream), "mcgmil_conv2d")
+            part = torch.empty((n.value, 3, a.out_channels), dtype=torch.float32, device=dev)
+            a.stats = _ptr(part)
+    _lib.check(L.mcgmil_conv2d(ctypes.byref(a), _stream(dev)), "mcgmil_conv2d")
     return (y, part) if stats else y
-
-
-def conv32_enabled() -> bool:
-    """MCGMIL_NATIVE_CONV32=0 keeps fp32 convolutions on the torch layers (MIOpen)."""
-    return os.environ.get("MCGMIL_NATIVE_CONV32", "1") != "0" and conv_enabled()
 
 
 def conv32_fusable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     """A CUDA channels-last fp32 activation (no autocast) and a convolution the fp32 kernel
     implements (mcgmil_conv2d_f32: out_channels % 64, kernel <= 7, and in_channels % 16 or
     kh * kw * in_channels <= 1024 -- the 3-channel stem), no autograd."""
-    if not (conv32_enabled() and isinstance(conv, nn.Conv2d) and x.is_cuda and x.dim() == 4):
-        return False
-    if x.dtype != torch.float32 or torch.is_autocast_enabled("cuda"):
-        return False
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return False
-    if _square(conv.dilation) != 1 or _square(conv.stride) is None or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return False
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7):
-        return False
-    if conv.out_channels % 64 or x.shape[1] != conv.in_channels:
-        return False
-    if conv.in_channels % 16 and kh * kw * conv.in_channels > 1024:
-        return False
-    if not x.is_contiguous(memory_format=torch.channels_last):
-        return False
-    if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
-        return False
-    oh = (x.shape[2] + 2 * _square(conv.padding) - kh) // _square(conv.stride) + 1
-    ow = (x.shape[3] + 2 * _square(conv.padding) - kw) // _square(conv.stride) + 1
-    return x.shape[0] * oh * ow < 2 ** 31 - 256
+    return _conv_refusal(conv, x, **_CONV32_FUSABLE) is None
 
 
 def packed_conv_weight_f32(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
@@ -286,9 +381,7 @@ def packed_conv_weight_f32(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     n = ctypes.c_size_t()
     _lib.check(L.mcgmil_conv_packed_size_f32(ctypes.byref(a), ctypes.byref(n)), "mcgmil_conv_packed_size_f32")
     packed = torch.empty(n.value, dtype=torch.float32, device=x.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_pack_conv_weights_f32(ctypes.byref(a), ctypes.c_void_p(w32.data_ptr()),
-                                              ctypes.c_void_p(packed.data_ptr()), stream),
+    _lib.check(L.mcgmil_pack_conv_weights_f32(ctypes.byref(a), _ptr(w32), _ptr(packed), _stream(x.device)),
                "mcgmil_pack_conv_weights_f32")
     conv._mcgmil_packed32 = (key, packed)
     return packed
@@ -312,26 +405,19 @@ def conv2d_f32(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
         raise ValueError("conv2d_f32 needs a CUDA channels-last fp32 activation and a bias-free groups=1 "
                          "convolution with out_channels % 64 == 0 (conv32_fusable)")
     L = _lib.load()
+    dev = x.device
     a = _conv_args(conv, x)
-    if in_ab is not None:
-        if in_ab.shape != (2, a.in_channels) or in_ab.dtype != torch.float32 or \
-                in_ab.device != x.device or not in_ab.is_contiguous():
-            raise ValueError("in_ab must be a contiguous fp32 [2, in_channels] tensor on x's device")
-        a.in_ab, a.in_relu = ctypes.c_void_p(in_ab.data_ptr()), int(bool(in_relu))
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    y = torch.empty((a.batch, a.out_channels, oh, ow), dtype=torch.float32, device=x.device,
-                    memory_format=torch.channels_last)
+    _set_in_ab(a, in_ab, in_relu, dev)
+    y = torch.empty(_conv_out_shape(a), dtype=torch.float32, device=dev, memory_format=_CL)
     w = packed_conv_weight_f32(conv, x)
-    a.x, a.w, a.y = (ctypes.c_void_p(t.data_ptr()) for t in (x, w, y))
+    a.x, a.w, a.y = _ptr(x), _ptr(w), _ptr(y)
     part = None
     if stats:
         n = ctypes.c_int32()
         _lib.check(L.mcgmil_conv_stats_parts_f32(ctypes.byref(a), ctypes.byref(n)), "mcgmil_conv_stats_parts_f32")
-        part = torch.empty((n.value, 3, a.out_channels), dtype=torch.float32, device=x.device)
-        a.stats = ctypes.c_void_p(part.data_ptr())
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_conv2d_f32(ctypes.byref(a), stream), "mcgmil_conv2d_f32")
+        part = torch.empty((n.value, 3, a.out_channels), dtype=torch.float32, device=dev)
+        a.stats = _ptr(part)
+    _lib.check(L.mcgmil_conv2d_f32(ctypes.byref(a), _stream(dev)), "mcgmil_conv2d_f32")
     return (y, part) if stats else y
 
 
@@ -358,25 +444,7 @@ def conv32_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     bias-free groups=1 dilation-1 zero-padded convolution with kernel 1..7, stride 1 or 2,
     pad < kernel, in_channels % 16 == 0 and out_channels % 64 == 0. Says nothing about autograd:
     that is what the kernels are for."""
-    if not (conv32_enabled() and isinstance(conv, nn.Conv2d) and x.is_cuda and x.dim() == 4):
-        return False
-    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32 or torch.is_autocast_enabled("cuda"):
-        return False
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return False
-    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return False
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
-        return False
-    if conv.in_channels % 16 or conv.out_channels % 64 or x.shape[1] != conv.in_channels:
-        return False
-    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
-        return False
-    s, p = _square(conv.stride), _square(conv.padding)
-    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
-    return oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256
+    return _conv_refusal(conv, x, **_CONV32_TRAINABLE) is None
 
 
 class _ConvShim(nn.Conv2d):
@@ -400,6 +468,25 @@ def flipped_weight(weight: torch.Tensor) -> torch.Tensor:
     return weight.flip(2, 3).transpose(0, 1).contiguous()
 
 
+def _wgrad(args_type, dy_dtype: torch.dtype, size_name: str, launch_name: str,
+           conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int) -> torch.Tensor:
+    """The three weight gradients after their predicates: dW [out, in, kh, kw] fp32 from x and dY."""
+    L = _lib.load()
+    dev = x.device
+    g = args_type()
+    g.fwd = _conv_args(conv, x)
+    a = g.fwd
+    if dy.shape != _conv_out_shape(a) or dy.dtype != dy_dtype or dy.device != dev:
+        raise ValueError(f"dy must be {_TWIN[dy_dtype].word} {_conv_out_shape(a)} on x's device")
+    dy = dy.contiguous(memory_format=_CL)
+    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=dev)
+    a.x, g.dy, g.dw = _ptr(x), _ptr(dy), _ptr(dw)
+    g.chunk_pixels = int(chunk_pixels)
+    _workspace(getattr(L, size_name), size_name, g, dev)
+    _lib.check(getattr(L, launch_name)(ctypes.byref(g), _stream(dev)), launch_name)
+    return dw
+
+
 def conv2d_f32_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
     """dW [out, in, kh, kw] fp32 of conv(x) given dY, on the HIP weight-gradient kernel
     (mcgmil_conv2d_wgrad_f32; see conv32_trainable). chunk_pixels caps the output pixels per
@@ -407,30 +494,8 @@ def conv2d_f32_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_p
     if not conv32_trainable(conv, x):
         raise ValueError("conv2d_f32_wgrad needs a CUDA channels-last fp32 activation and a convolution "
                          "the weight-gradient kernel implements (see conv32_trainable)")
-    L = _lib.load()
-    g = _lib.ConvGradArgs()
-    a = g.fwd
-    a.batch, _, a.height, a.width = x.shape
-    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
-    a.kernel_h, a.kernel_w = conv.kernel_size
-    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.float32 or dy.device != x.device:
-        raise ValueError(f"dy must be fp32 {(a.batch, a.out_channels, oh, ow)} on x's device")
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
-    a.x = ctypes.c_void_p(x.data_ptr())
-    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
-    g.chunk_pixels = int(chunk_pixels)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_conv_wgrad_workspace_size_f32(ctypes.byref(g), ctypes.byref(n)),
-               "mcgmil_conv_wgrad_workspace_size_f32")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
-    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_conv2d_wgrad_f32(ctypes.byref(g), stream), "mcgmil_conv2d_wgrad_f32")
-    return dw
+    return _wgrad(_lib.ConvGradArgs, torch.float32, "mcgmil_conv_wgrad_workspace_size_f32", "mcgmil_conv2d_wgrad_f32",
+                  conv, x, dy, chunk_pixels)
 
 
 def dgrad_native(conv: nn.Conv2d) -> bool:
@@ -497,20 +562,7 @@ def dgrad_direct_supported(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
     fp32 dy [batch, out_channels, OH, OW] without autocast, and a bias-free groups=1 dilation-1
     zero-padded convolution with kernel 1..7 per axis, stride 1 or 2, pad < kernel,
     in_channels % 16 == 0 and out_channels % 64 == 0 (include/mcgmil_conv_dgrad.h)."""
-    if not (conv32_enabled() and isinstance(conv, nn.Conv2d) and dy.is_cuda and dy.dim() == 4):
-        return False
-    if dy.dtype != torch.float32 or conv.weight.dtype != torch.float32 or torch.is_autocast_enabled("cuda"):
-        return False
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return False
-    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return False
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
-        return False
-    return conv.in_channels % 16 == 0 and conv.out_channels % 64 == 0 and dy.shape[1] == conv.out_channels and \
-        dy.numel() > 0
+    return _conv_refusal(conv, dy, **_DGRAD_DIRECT) is None
 
 
 def conv2d_f32_dgrad_direct(conv: nn.Conv2d, dy: torch.Tensor, x_shape) -> torch.Tensor:
@@ -524,21 +576,15 @@ def conv2d_f32_dgrad_direct(conv: nn.Conv2d, dy: torch.Tensor, x_shape) -> torch
                          "kernel implements (see dgrad_direct_supported)")
     L = _lib.load()
     g = _lib.ConvDgradArgs()
-    a = g.fwd
-    a.batch, cin, a.height, a.width = (int(v) for v in x_shape)
-    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
-    a.kernel_h, a.kernel_w = conv.kernel_size
-    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    if cin != conv.in_channels or tuple(dy.shape) != (a.batch, a.out_channels, oh, ow):
+    g.fwd = _conv_args(conv, x_shape)
+    if int(x_shape[1]) != conv.in_channels or tuple(dy.shape) != _conv_out_shape(g.fwd):
         raise ValueError(f"x_shape {tuple(x_shape)} does not belong to this convolution and dy {tuple(dy.shape)}")
-    dy = dy.contiguous(memory_format=torch.channels_last)
+    dy = dy.contiguous(memory_format=_CL)
     wt = conv.weight.detach().permute(2, 3, 0, 1).contiguous()           # [kh][kw][out][in]
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device, memory_format=torch.channels_last)
-    g.dy, g.w_t, g.dx = (ctypes.c_void_p(t.data_ptr()) for t in (dy, wt, dx))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dy.device).cuda_stream)
-    _lib.check(L.mcgmil_conv2d_dgrad_f32(ctypes.byref(g), stream), "mcgmil_conv2d_dgrad_f32")
+    dev = dy.device
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dev, memory_format=_CL)
+    g.dy, g.w_t, g.dx = _ptr(dy), _ptr(wt), _ptr(dx)
+    _lib.check(L.mcgmil_conv2d_dgrad_f32(ctypes.byref(g), _stream(dev)), "mcgmil_conv2d_dgrad_f32")
     return dx
 
 
@@ -584,10 +630,14 @@ def conv2d_f32_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need
     return dx, dw
 
 
+def _conv_op(name: str, layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    return getattr(torch.ops.mcgmil, name)(x, layer.weight, _square(layer.stride), _square(layer.padding))
+
+
 def conv2d_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """layer(x) through the differentiable op torch.ops.mcgmil.conv2d_f32 (mcgmil.library)."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    return torch.ops.mcgmil.conv2d_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
+    return _conv_op("conv2d_f32", layer, x)
 
 
 # ---------------------------------------------------------------- fp32 stem convolution backward
@@ -612,37 +662,7 @@ def stem_conv_untrainable_reason(conv: nn.Conv2d, x: torch.Tensor) -> Optional[s
     """Why conv on x is not a convolution whose forward AND weight gradient run on the fp32 HIP
     kernels for few input channels (include/mcgmil_stem_grad.h), or None when it is. The conditions
     are those of conv32_trainable with 1 <= in_channels <= 4 in place of in_channels % 16 == 0."""
-    if not conv32_enabled():
-        return "the native fp32 convolutions are switched off (MCGMIL_NATIVE_CONV32 / MCGMIL_NATIVE_CONV)"
-    if not isinstance(conv, nn.Conv2d):
-        return "not an nn.Conv2d"
-    if not (x.is_cuda and x.dim() == 4):
-        return "the activation is not a 4-d CUDA tensor"
-    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32:
-        return "the activation and the weight must be fp32"
-    if torch.is_autocast_enabled("cuda"):
-        return "autocast is enabled"
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return "only a bias-free groups=1 zero-padded convolution"
-    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return "dilation 1, a square stride of 1 or 2 and a square integer padding"
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
-        return "kernel 1..7 per axis and pad < min(kh, kw)"
-    if not 1 <= conv.in_channels <= 4:
-        return "in_channels must be in 1..4"
-    if conv.out_channels % 64 or conv.out_channels > 4096:
-        return "out_channels must be a multiple of 64 (at most 4096)"
-    if x.shape[1] != conv.in_channels:
-        return "the activation's channels are not the convolution's in_channels"
-    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
-        return "the activation must be non-empty and channels-last"
-    s, p = _square(conv.stride), _square(conv.padding)
-    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
-    if not (oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256):
-        return "batch * OH * OW must be in 1 .. 2^31 - 257"
-    return None
+    return _conv_refusal(conv, x, **_STEM_CONV_TRAINABLE)
 
 
 def stem_conv_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -657,36 +677,13 @@ def conv2d_f32_stem_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, ch
     reason = stem_conv_untrainable_reason(conv, x)
     if reason is not None:
         raise ValueError(f"conv2d_f32_stem_wgrad: {reason} (see stem_conv_trainable)")
-    L = _lib.load()
-    g = _lib.ConvGradArgs()
-    a = g.fwd
-    a.batch, _, a.height, a.width = x.shape
-    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
-    a.kernel_h, a.kernel_w = conv.kernel_size
-    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.float32 or dy.device != x.device:
-        raise ValueError(f"dy must be fp32 {(a.batch, a.out_channels, oh, ow)} on x's device")
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
-    a.x = ctypes.c_void_p(x.data_ptr())
-    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
-    g.chunk_pixels = int(chunk_pixels)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_stem_wgrad_workspace_size_f32(ctypes.byref(g), ctypes.byref(n)),
-               "mcgmil_stem_wgrad_workspace_size_f32")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
-    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_stem_wgrad_f32(ctypes.byref(g), stream), "mcgmil_stem_wgrad_f32")
-    return dw
+    return _wgrad(_lib.ConvGradArgs, torch.float32, "mcgmil_stem_wgrad_workspace_size_f32", "mcgmil_stem_wgrad_f32",
+                  conv, x, dy, chunk_pixels)
 
 
 def stem_conv_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """layer(x) through the differentiable op torch.ops.mcgmil.stem_conv_f32 (mcgmil.library)."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    return torch.ops.mcgmil.stem_conv_f32(x, layer.weight, _square(layer.stride), _square(layer.padding))
+    return _conv_op("stem_conv_f32", layer, x)
 
 
 # ---------------------------------------------------------------- bf16 convolution backward
@@ -714,39 +711,7 @@ def conv_bf16_untrainable_reason(conv: nn.Conv2d, x: torch.Tensor) -> Optional[s
     channels-last bf16 activation below 2 GiB, an fp32 (master) or bf16 weight, a bias-free groups=1
     dilation-1 zero-padded convolution with kernel 1..7, stride 1 or 2, pad < kernel and
     in_channels and out_channels multiples of 64. Says nothing about autograd or autocast."""
-    if not conv_enabled():
-        return "the native convolutions are switched off (MCGMIL_NATIVE_CONV)"
-    if not isinstance(conv, nn.Conv2d):
-        return "not an nn.Conv2d"
-    if not (x.is_cuda and x.dim() == 4):
-        return "the activation is not a 4-d CUDA tensor"
-    if x.dtype != torch.bfloat16:
-        return "the activation must be bf16"
-    if conv.weight.dtype not in (torch.float32, torch.bfloat16):
-        return "the weight must be fp32 or bf16"
-    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
-        return "only a bias-free groups=1 zero-padded convolution"
-    if _square(conv.dilation) != 1 or _square(conv.stride) not in (1, 2) or \
-            not isinstance(conv.padding, tuple) or _square(conv.padding) is None:
-        return "dilation 1, a square stride of 1 or 2 and a square integer padding"
-    kh, kw = conv.kernel_size
-    if not (1 <= kh <= 7 and 1 <= kw <= 7) or _square(conv.padding) >= min(kh, kw):
-        return "kernel 1..7 per axis and pad < min(kh, kw)"
-    if conv.in_channels % 64:
-        return "in_channels must be a multiple of 64"
-    if conv.out_channels % 64:
-        return "out_channels must be a multiple of 64"
-    if x.shape[1] != conv.in_channels:
-        return "the activation's channels are not the convolution's in_channels"
-    if x.numel() == 0 or not x.is_contiguous(memory_format=torch.channels_last):
-        return "the activation must be non-empty and channels-last"
-    s, p = _square(conv.stride), _square(conv.padding)
-    oh, ow = (x.shape[2] + 2 * p - kh) // s + 1, (x.shape[3] + 2 * p - kw) // s + 1
-    if not (oh >= 1 and ow >= 1 and x.shape[0] * oh * ow < 2 ** 31 - 256):
-        return "batch * OH * OW must be in 1 .. 2^31 - 257"
-    if x.numel() * 2 >= 2 ** 31 or max(x.shape[2], x.shape[3]) > 16383:
-        return "the activation must be smaller than 2 GiB, height and width at most 16383"
-    return None
+    return _conv_refusal(conv, x, **_CONV_BF16_TRAINABLE)
 
 
 def conv_bf16_trainable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -772,30 +737,8 @@ def conv2d_bf16_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_
     reason = conv_bf16_untrainable_reason(conv, x)
     if reason is not None:
         raise ValueError(f"conv2d_bf16_wgrad: {reason} (see conv_bf16_trainable)")
-    L = _lib.load()
-    g = _lib.ConvGradBf16Args()
-    a = g.fwd
-    a.batch, _, a.height, a.width = x.shape
-    a.in_channels, a.out_channels = conv.in_channels, conv.out_channels
-    a.kernel_h, a.kernel_w = conv.kernel_size
-    a.stride, a.pad = _square(conv.stride), _square(conv.padding)
-    oh = (a.height + 2 * a.pad - a.kernel_h) // a.stride + 1
-    ow = (a.width + 2 * a.pad - a.kernel_w) // a.stride + 1
-    if dy.shape != (a.batch, a.out_channels, oh, ow) or dy.dtype != torch.bfloat16 or dy.device != x.device:
-        raise ValueError(f"dy must be bf16 {(a.batch, a.out_channels, oh, ow)} on x's device")
-    dy = dy.contiguous(memory_format=torch.channels_last)
-    dw = torch.empty((a.out_channels, a.in_channels, a.kernel_h, a.kernel_w), dtype=torch.float32, device=x.device)
-    a.x = ctypes.c_void_p(x.data_ptr())
-    g.dy, g.dw = ctypes.c_void_p(dy.data_ptr()), ctypes.c_void_p(dw.data_ptr())
-    g.chunk_pixels = int(chunk_pixels)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_conv_wgrad_workspace_size_bf16(ctypes.byref(g), ctypes.byref(n)),
-               "mcgmil_conv_wgrad_workspace_size_bf16")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=x.device)     # freed after the launches,
-    g.workspace, g.workspace_bytes = ctypes.c_void_p(ws.data_ptr()), n.value    # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_conv2d_wgrad_bf16(ctypes.byref(g), stream), "mcgmil_conv2d_wgrad_bf16")
-    return dw
+    return _wgrad(_lib.ConvGradBf16Args, torch.bfloat16, "mcgmil_conv_wgrad_workspace_size_bf16",
+                  "mcgmil_conv2d_wgrad_bf16", conv, x, dy, chunk_pixels)
 
 
 def dgrad_bf16_native(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
@@ -852,8 +795,7 @@ def conv2d_bf16_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, nee
 
 def conv2d_bf16_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     """layer(x) through the differentiable op torch.ops.mcgmil.conv2d_bf16 (mcgmil.library)."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    return torch.ops.mcgmil.conv2d_bf16(x, layer.weight, _square(layer.stride), _square(layer.padding))
+    return _conv_op("conv2d_bf16", layer, x)
 
 
 def _native_conv(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
@@ -916,6 +858,7 @@ def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     return torch_conv(layer, x)
 
 
+# ---------------------------------------------------------------- fused BatchNorm (+ add) (+ ReLU) (+ pool)
 def _f32(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
     if t is None:
         return None
@@ -929,12 +872,38 @@ def _pool_params(pool) -> Optional[tuple]:
     """(k, stride, pad) of a plain square nn.MaxPool2d the kernel can fuse, else None."""
     if not isinstance(pool, nn.MaxPool2d) or pool.ceil_mode or pool.return_indices:
         return None
-    sq = lambda v: v if isinstance(v, int) else (v[0] if len(set(v)) == 1 else None)  # noqa: E731
-    k, st = sq(pool.kernel_size), sq(pool.stride if pool.stride is not None else pool.kernel_size)
-    pd, dil = sq(pool.padding), sq(pool.dilation)
+    k, st = _square(pool.kernel_size), _square(pool.stride if pool.stride is not None else pool.kernel_size)
+    pd, dil = _square(pool.padding), _square(pool.dilation)
     if None in (k, st, pd, dil) or dil != 1 or k < 1 or st < 1 or pd < 0 or 2 * pd > k:
         return None
     return k, st, pd
+
+
+def _bn_tensors(bn: nn.BatchNorm2d, dev):
+    """(uses batch statistics, gamma, beta, running mean, running var) of a layer as the kernels
+    take them: fp32 on dev, None where the layer has none or normalises with the batch's."""
+    use_batch = _use_batch(bn)
+    return (use_batch, _f32(bn.weight, dev) if bn.affine else None, _f32(bn.bias, dev) if bn.affine else None,
+            None if use_batch else _f32(bn.running_mean, dev), None if use_batch else _f32(bn.running_var, dev))
+
+
+def _bn_args(x: torch.Tensor, gamma, beta, eps: float, relu: bool = False, rmean=None, rvar=None) -> "_lib.BnArgs":
+    """mcgmil_bn_args for the channels-last [N, C, H, W] activation x and its layer's tensors."""
+    N, C, H, W = x.shape
+    a = _lib.BnArgs()
+    a.rows, a.channels, a.dtype = N * H * W, C, _DT[x.dtype]
+    a.batch, a.height, a.width = N, H, W
+    a.x = _ptr(x)
+    a.gamma, a.beta, a.running_mean, a.running_var = _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar)
+    a.eps, a.relu = float(eps), int(bool(relu))
+    return a
+
+
+def _set_partials(a: "_lib.BnArgs", partials: torch.Tensor, dev) -> None:
+    if partials.dim() != 3 or partials.shape[1:] != (3, a.channels) or not partials.is_contiguous() or \
+            partials.dtype != torch.float32 or partials.device != dev:
+        raise ValueError("partials must be a contiguous fp32 [parts, 3, C] tensor on x's device")
+    a.partials, a.num_partials = _ptr(partials), partials.shape[0]
 
 
 def batchnorm_act(x: torch.Tensor, bn: nn.BatchNorm2d, relu: bool,
@@ -958,42 +927,25 @@ def batchnorm_act(x: torch.Tensor, bn: nn.BatchNorm2d, relu: bool,
                              "residual, is fused")
     L = _lib.load()
     dev = x.device
-    N, C, H, W = x.shape
-    use_batch = bn.training or bn.running_mean is None or bn.running_var is None
-    gamma = _f32(bn.weight, dev) if bn.affine else None
-    beta = _f32(bn.bias, dev) if bn.affine else None
-    rmean = None if use_batch else _f32(bn.running_mean, dev)
-    rvar = None if use_batch else _f32(bn.running_var, dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _DT[x.dtype]
-    a.batch, a.height, a.width = N, H, W
+    use_batch, gamma, beta, rmean, rvar = _bn_tensors(bn, dev)
+    a = _bn_args(x, gamma, beta, bn.eps, relu, rmean, rvar)
+    N, C, H, W = a.batch, a.channels, a.height, a.width
     if pp is None:
         y = torch.empty_like(x, memory_format=torch.channels_last)
     else:
         k, st, pd = pp
-        Ho, Wo = (H + 2 * pd - k) // st + 1, (W + 2 * pd - k) // st + 1
-        y = torch.empty((N, C, Ho, Wo), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
+        y = torch.empty((N, C) + _out_hw(H, W, k, k, st, pd), dtype=x.dtype, device=dev, memory_format=_CL)
         a.pool_kernel, a.pool_stride, a.pool_pad = k, st, pd
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y, a.residual = p(x), p(y), p(residual)
-    a.gamma, a.beta, a.running_mean, a.running_var = p(gamma), p(beta), p(rmean), p(rvar)
-    a.eps, a.relu = float(bn.eps), int(bool(relu))
+    a.y, a.residual = _ptr(y), _ptr(residual)
     if residual_ab is not None:
         if residual is None or residual_ab.shape != (2, C) or residual_ab.dtype != torch.float32 or \
                 residual_ab.device != dev or not residual_ab.is_contiguous():
             raise ValueError("residual_ab needs a residual and a contiguous fp32 [2, C] tensor on x's device")
-        a.residual_ab = p(residual_ab)
+        a.residual_ab = _ptr(residual_ab)
     if partials is not None and use_batch:
-        if partials.dim() != 3 or partials.shape[1:] != (3, C) or not partials.is_contiguous() or \
-                partials.dtype != torch.float32 or partials.device != dev:
-            raise ValueError("partials must be a contiguous fp32 [parts, 3, C] tensor on x's device")
-        a.partials, a.num_partials = p(partials), partials.shape[0]
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    a.workspace, a.workspace_bytes = p(ws), n.value
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), stream), "mcgmil_batchnorm_act")
+        _set_partials(a, partials, dev)
+    _workspace(L.mcgmil_bn_workspace_size, "mcgmil_bn_workspace_size", a, dev)
+    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), _stream(dev)), "mcgmil_batchnorm_act")
     return y
 
 
@@ -1005,34 +957,15 @@ def batchnorm_coefficients(x: torch.Tensor, bn: nn.BatchNorm2d,
         raise ValueError("batchnorm_coefficients needs what batchnorm_act needs (see fusable)")
     L = _lib.load()
     dev = x.device
-    N, C, H, W = x.shape
-    use_batch = bn.training or bn.running_mean is None or bn.running_var is None
-    gamma = _f32(bn.weight, dev) if bn.affine else None
-    beta = _f32(bn.bias, dev) if bn.affine else None
-    rmean = None if use_batch else _f32(bn.running_mean, dev)
-    rvar = None if use_batch else _f32(bn.running_var, dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _DT[x.dtype]
-    a.batch, a.height, a.width = N, H, W
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x = p(x)
-    a.gamma, a.beta, a.running_mean, a.running_var = p(gamma), p(beta), p(rmean), p(rvar)
-    a.eps = float(bn.eps)
-    ws = None
+    use_batch, gamma, beta, rmean, rvar = _bn_tensors(bn, dev)
+    a = _bn_args(x, gamma, beta, bn.eps, False, rmean, rvar)
     if partials is not None and use_batch:
-        if partials.dim() != 3 or partials.shape[1:] != (3, C) or not partials.is_contiguous() or \
-                partials.dtype != torch.float32 or partials.device != dev:
-            raise ValueError("partials must be a contiguous fp32 [parts, 3, C] tensor on x's device")
-        a.partials, a.num_partials = p(partials), partials.shape[0]
+        _set_partials(a, partials, dev)
     if use_batch:     # the statistics pass, or more than 1024 partials combined in chunks first
-        n = ctypes.c_size_t()
         a.y = a.x
-        _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-        ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-        a.workspace, a.workspace_bytes = p(ws), n.value
-    ab = torch.empty((2, C), dtype=torch.float32, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_coefficients(ctypes.byref(a), p(ab), stream), "mcgmil_batchnorm_coefficients")
+        _workspace(L.mcgmil_bn_workspace_size, "mcgmil_bn_workspace_size", a, dev)
+    ab = torch.empty((2, a.channels), dtype=torch.float32, device=dev)
+    _lib.check(L.mcgmil_batchnorm_coefficients(ctypes.byref(a), _ptr(ab), _stream(dev)), "mcgmil_batchnorm_coefficients")
     return ab
 
 
@@ -1054,13 +987,13 @@ def native_norm_training(flag: bool = True):
         _native_norm_training = before
 
 
-def bn_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None) -> Optional[str]:
-    """Why `bn_trainable` refuses (x, bn, residual), or None when it holds. The device is checked
-    last, so the other clauses can be seen on a machine without a GPU."""
+def _bn_refusal(x: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor], dtype: torch.dtype) -> Optional[str]:
+    """Why (x, bn, residual) is outside the fused BatchNorm training op of `dtype`, or None. The
+    fp32 op refuses autocast; the bf16 one takes what autocast gives it and never asks."""
     if not isinstance(bn, nn.BatchNorm2d) or x.dim() != 4:
         return "layer: an nn.BatchNorm2d on a 4-D activation"
-    if x.dtype != torch.float32 or any(p is not None and p.dtype != torch.float32 for p in (bn.weight, bn.bias)):
-        return "dtype: fp32 only"
+    if x.dtype != dtype or any(p is not None and p.dtype != torch.float32 for p in (bn.weight, bn.bias)):
+        return "dtype: fp32 only" if dtype == torch.float32 else "dtype: a bf16 activation with fp32 parameters"
     C = x.shape[1]
     if C % 8 or C > 2048 or C != bn.num_features:
         return "channels: C % 8 == 0, C <= 2048, C == bn.num_features"
@@ -1075,9 +1008,15 @@ def bn_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optional[tor
         return "residual: x's shape, dtype and device"
     if not x.is_cuda or any(p is not None and p.device != x.device for p in (bn.weight, bn.bias)):
         return "device: a CUDA activation with the parameters on its device"
-    if torch.is_autocast_enabled("cuda"):
+    if dtype == torch.float32 and torch.is_autocast_enabled("cuda"):
         return "autocast"
     return None
+
+
+def bn_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optional[torch.Tensor] = None) -> Optional[str]:
+    """Why `bn_trainable` refuses (x, bn, residual), or None when it holds. The device is checked
+    last, so the other clauses can be seen on a machine without a GPU."""
+    return _bn_refusal(x, bn, residual, torch.float32)
 
 
 def bn_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[torch.Tensor] = None) -> bool:
@@ -1092,12 +1031,12 @@ def bn_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[torch.T
     return bn_untrainable_reason(x, bn, residual) is None
 
 
-def _check_rows_c(name: str, x: torch.Tensor, **like) -> None:
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[1] % 8 == 0 and
+def _check_rows_c(name: str, dtype: torch.dtype, x: torch.Tensor, **like) -> None:
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == dtype and x.shape[1] % 8 == 0 and
             x.shape[1] <= 2048 and x.numel() >= 2 * x.shape[1] and
             x.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError(f"{name} needs a CUDA channels-last fp32 [N, C, H, W] activation with C % 8 == 0, "
-                         "C <= 2048 and at least 2 values per channel")
+        raise ValueError(f"{name} needs a CUDA channels-last {_TWIN[dtype].word} [N, C, H, W] activation with "
+                         "C % 8 == 0, C <= 2048 and at least 2 values per channel")
     for n, t in like.items():
         if t is not None and (t.shape != x.shape or t.dtype != x.dtype or t.device != x.device or
                               not t.is_contiguous(memory_format=torch.channels_last)):
@@ -1111,34 +1050,93 @@ def _check_per_channel(name: str, C: int, dev, **vecs) -> None:
             raise ValueError(f"{name}: {n} must be a contiguous fp32 [{C}] tensor on x's device")
 
 
+def _pool_grad_geometry(k: int, stride: int, pad: int) -> bool:
+    """The pool geometry of include/mcgmil_pool_grad.h: k in {2, 3}, 1 <= stride <= k, 0 <= pad <= k / 2."""
+    return k in (2, 3) and 1 <= stride <= k and 0 <= pad and 2 * pad <= k
+
+
+def _bn_stats(dtype: torch.dtype, base: str, x: torch.Tensor, weight: Optional[torch.Tensor],
+              bias: Optional[torch.Tensor], residual: Optional[torch.Tensor], eps: float, relu: bool,
+              pool: Optional[tuple] = None):
+    """The forward of the four BatchNorm training ops, `base` + the dtype's suffix: (y, mean, invstd)
+    from mcgmil_batchnorm_act with batch_mean / batch_invstd requested, or with pool = (k, stride,
+    pad) (y, mean, invstd, argmax) from mcgmil_batchnorm_pool_train[_bf16]."""
+    twin = _TWIN[dtype]
+    name = base + twin.suffix
+    _check_rows_c(name, dtype, x, residual=residual)
+    if pool is not None and not _pool_grad_geometry(*pool):
+        raise ValueError(f"{name} needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
+                         "0 <= pad <= kernel / 2")
+    L = _lib.load()
+    dev = x.device
+    a = _bn_args(x, weight, bias, eps, relu)
+    N, C, H, W = shape = a.batch, a.channels, a.height, a.width
+    if pool is not None:
+        k, stride, pad = pool
+        shape = (N, C) + _out_hw(H, W, k, k, stride, pad)
+        if shape[2] < 1 or shape[3] < 1:
+            raise ValueError(f"{name}: the pooling window is larger than the padded input")
+    _check_per_channel(name, C, dev, weight=weight, bias=bias)
+    y = torch.empty(shape, dtype=dtype, device=dev, memory_format=_CL)
+    mean = torch.empty(C, dtype=torch.float32, device=dev)
+    invstd = torch.empty(C, dtype=torch.float32, device=dev)
+    a.y, a.residual = _ptr(y), _ptr(residual)
+    a.batch_mean, a.batch_invstd = _ptr(mean), _ptr(invstd)
+    if pool is None:
+        _workspace(L.mcgmil_bn_workspace_size, "mcgmil_bn_workspace_size", a, dev)
+        _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), _stream(dev)), "mcgmil_batchnorm_act")
+        return y, mean, invstd
+    a.pool_kernel, a.pool_stride, a.pool_pad = pool
+    argmax = torch.empty(shape, dtype=torch.uint8, device=dev, memory_format=_CL)
+    _workspace(L.mcgmil_bn_workspace_size, "mcgmil_bn_workspace_size", a, dev)
+    launch = "mcgmil_batchnorm_pool_train" + twin.suffix
+    _lib.check(getattr(L, launch)(ctypes.byref(a), _ptr(argmax), _stream(dev)), launch)
+    return y, mean, invstd, argmax
+
+
+def _bn_act_backward(dtype: torch.dtype, x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
+    """batchnorm_act_backward and batchnorm_act_backward_bf16."""
+    twin = _TWIN[dtype]
+    name = "batchnorm_act_backward" + twin.suffix
+    _check_rows_c(name, dtype, x, y=y if relu else None, dy=dy)
+    if relu and y is None:
+        raise ValueError(f"{name}: relu needs y (the forward's output)")
+    need_dres = bool(need_dres and relu)
+    if not (need_dx or need_dres or need_dw):
+        return None, None, None, None
+    L = _lib.load()
+    dev = x.device
+    N, C, H, W = x.shape
+    _check_per_channel(name, C, dev, weight=weight, mean=mean, invstd=invstd)
+    dx = torch.empty_like(x, memory_format=torch.channels_last) if need_dx else None
+    dres = torch.empty_like(x, memory_format=torch.channels_last) if need_dres else None
+    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    a = twin.bn_grad_args()
+    a.rows, a.channels, a.relu = N * H * W, C, int(bool(relu))
+    a.x, a.y, a.dy = _ptr(x), _ptr(y if relu else None), _ptr(dy)
+    a.gamma, a.mean, a.invstd = _ptr(weight), _ptr(mean), _ptr(invstd)
+    a.dx, a.dresidual, a.dgamma, a.dbeta = _ptr(dx), _ptr(dres), _ptr(dw), _ptr(db)
+    size, launch = "mcgmil_bn_grad_workspace_size" + twin.suffix, "mcgmil_batchnorm_act_backward" + twin.suffix
+    _workspace(getattr(L, size), size, a, dev)
+    _lib.check(getattr(L, launch)(ctypes.byref(a), _stream(dev)), launch)
+    return dx, dres, dw, db
+
+
+def _bn_act_op(op: str, bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, residual: Optional[torch.Tensor]):
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    x = x.contiguous(memory_format=torch.channels_last)
+    if residual is not None:
+        residual = residual.contiguous(memory_format=torch.channels_last)
+    return getattr(torch.ops.mcgmil, op)(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
+
+
 def batchnorm_act_stats(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
                         residual: Optional[torch.Tensor], eps: float, relu: bool):
     """(y, mean [C], invstd [C]) of relu?(batch_norm(x) [+ residual]) on the batch statistics of x
     (fp32, channels-last): mcgmil_batchnorm_act with batch_mean / batch_invstd requested and the
     statistics from its own pass over x. What the backward (batchnorm_act_backward) needs."""
-    _check_rows_c("batchnorm_act_stats", x, residual=residual)
-    L = _lib.load()
-    dev = x.device
-    N, C, H, W = x.shape
-    _check_per_channel("batchnorm_act_stats", C, dev, weight=weight, bias=bias)
-    y = torch.empty_like(x, memory_format=torch.channels_last)
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_F32
-    a.batch, a.height, a.width = N, H, W
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y, a.residual = p(x), p(y), p(residual)
-    a.gamma, a.beta = p(weight), p(bias)
-    a.eps, a.relu = float(eps), int(bool(relu))
-    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    a.workspace, a.workspace_bytes = p(ws), n.value
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), stream), "mcgmil_batchnorm_act")
-    return y, mean, invstd
+    return _bn_stats(torch.float32, "batchnorm_act_stats", x, weight, bias, residual, eps, relu)
 
 
 def batchnorm_act_backward(x: torch.Tensor, y: Optional[torch.Tensor], dy: torch.Tensor,
@@ -1148,44 +1146,14 @@ def batchnorm_act_backward(x: torch.Tensor, y: Optional[torch.Tensor], dy: torch
     (mcgmil_batchnorm_act_backward, include/mcgmil_bn_grad.h). y is the forward's output, read for
     the ReLU mask only (None without ReLU). dresidual exists with ReLU only: without it the
     residual's gradient is dy itself and the caller passes dy on."""
-    _check_rows_c("batchnorm_act_backward", x, y=y if relu else None, dy=dy)
-    if relu and y is None:
-        raise ValueError("batchnorm_act_backward: relu needs y (the forward's output)")
-    need_dres = bool(need_dres and relu)
-    if not (need_dx or need_dres or need_dw):
-        return None, None, None, None
-    L = _lib.load()
-    dev = x.device
-    N, C, H, W = x.shape
-    _check_per_channel("batchnorm_act_backward", C, dev, weight=weight, mean=mean, invstd=invstd)
-    dx = torch.empty_like(x, memory_format=torch.channels_last) if need_dx else None
-    dres = torch.empty_like(x, memory_format=torch.channels_last) if need_dres else None
-    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    a = _lib.BnGradArgs()
-    a.rows, a.channels, a.relu = N * H * W, C, int(bool(relu))
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y, a.dy = p(x), p(y if relu else None), p(dy)
-    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
-    a.dx, a.dresidual, a.dgamma, a.dbeta = p(dx), p(dres), p(dw), p(db)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_grad_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_grad_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_act_backward(ctypes.byref(a), stream), "mcgmil_batchnorm_act_backward")
-    return dx, dres, dw, db
+    return _bn_act_backward(torch.float32, x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw)
 
 
 def bn_act_f32_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
                   residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """relu?(bn(x) [+ residual]) through the differentiable op torch.ops.mcgmil.bn_act_f32
     (mcgmil.library); the activation and the residual are made channels-last first if they are not."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    x = x.contiguous(memory_format=torch.channels_last)
-    if residual is not None:
-        residual = residual.contiguous(memory_format=torch.channels_last)
-    return torch.ops.mcgmil.bn_act_f32(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
+    return _bn_act_op("bn_act_f32", bn, x, relu, residual)
 
 
 # ---------------------------------------------------------------- fused bf16 BatchNorm backward
@@ -1212,25 +1180,7 @@ def bn_bf16_untrainable_reason(x: torch.Tensor, bn: nn.Module, residual: Optiona
     `bn_untrainable_reason` with a bf16 activation and residual, fp32 (master) parameters or none,
     and no autocast clause (the op takes what autocast gives it). The device is checked last, so
     the other clauses can be seen on a machine without a GPU."""
-    if not isinstance(bn, nn.BatchNorm2d) or x.dim() != 4:
-        return "layer: an nn.BatchNorm2d on a 4-D activation"
-    if x.dtype != torch.bfloat16 or any(p is not None and p.dtype != torch.float32 for p in (bn.weight, bn.bias)):
-        return "dtype: a bf16 activation with fp32 parameters"
-    C = x.shape[1]
-    if C % 8 or C > 2048 or C != bn.num_features:
-        return "channels: C % 8 == 0, C <= 2048, C == bn.num_features"
-    if x.numel() < 2 * C:
-        return "rows: at least 2 values per channel"
-    if not _use_batch(bn):
-        return "statistics: running-statistics mode"
-    if bn.training and bn.track_running_stats and bn.running_mean is not None:
-        return "statistics: a running-statistics update is pending"     # torch would update them
-    if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or
-                                 residual.device != x.device):
-        return "residual: x's shape, dtype and device"
-    if not x.is_cuda or any(p is not None and p.device != x.device for p in (bn.weight, bn.bias)):
-        return "device: a CUDA activation with the parameters on its device"
-    return None
+    return _bn_refusal(x, bn, residual, torch.bfloat16)
 
 
 def bn_bf16_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[torch.Tensor] = None) -> bool:
@@ -1240,47 +1190,13 @@ def bn_bf16_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, residual: Optional[to
     return bn_bf16_untrainable_reason(x, bn, residual) is None
 
 
-def _check_rows_c_bf16(name: str, x: torch.Tensor, **like) -> None:
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and
-            x.shape[1] <= 2048 and x.numel() >= 2 * x.shape[1] and
-            x.is_contiguous(memory_format=torch.channels_last)):
-        raise ValueError(f"{name} needs a CUDA channels-last bf16 [N, C, H, W] activation with C % 8 == 0, "
-                         "C <= 2048 and at least 2 values per channel")
-    for n, t in like.items():
-        if t is not None and (t.shape != x.shape or t.dtype != x.dtype or t.device != x.device or
-                              not t.is_contiguous(memory_format=torch.channels_last)):
-            raise ValueError(f"{name}: {n} must be channels-last with x's shape, dtype and device")
-
-
 def batchnorm_act_stats_bf16(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
                              residual: Optional[torch.Tensor], eps: float, relu: bool):
     """(y bf16, mean [C] fp32, invstd [C] fp32) of relu?(batch_norm(x) [+ residual]) on the batch
     statistics of x (bf16, channels-last; weight and bias fp32): mcgmil_batchnorm_act with
     MCGMIL_BF16, batch_mean / batch_invstd requested and the statistics from its own pass over x.
     What the backward (batchnorm_act_backward_bf16) needs."""
-    _check_rows_c_bf16("batchnorm_act_stats_bf16", x, residual=residual)
-    L = _lib.load()
-    dev = x.device
-    N, C, H, W = x.shape
-    _check_per_channel("batchnorm_act_stats_bf16", C, dev, weight=weight, bias=bias)
-    y = torch.empty_like(x, memory_format=torch.channels_last)
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_BF16
-    a.batch, a.height, a.width = N, H, W
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y, a.residual = p(x), p(y), p(residual)
-    a.gamma, a.beta = p(weight), p(bias)
-    a.eps, a.relu = float(eps), int(bool(relu))
-    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_act(ctypes.byref(a), stream), "mcgmil_batchnorm_act")
-    return y, mean, invstd
+    return _bn_stats(torch.bfloat16, "batchnorm_act_stats", x, weight, bias, residual, eps, relu)
 
 
 def batchnorm_act_backward_bf16(x: torch.Tensor, y: Optional[torch.Tensor], dy: torch.Tensor,
@@ -1291,45 +1207,14 @@ def batchnorm_act_backward_bf16(x: torch.Tensor, y: Optional[torch.Tensor], dy: 
     include/mcgmil_bn_grad_bf16.h). y is the forward's output, read for the ReLU mask only (None
     without ReLU). dresidual exists with ReLU only: without it the residual's gradient is dy itself
     and the caller passes dy on."""
-    _check_rows_c_bf16("batchnorm_act_backward_bf16", x, y=y if relu else None, dy=dy)
-    if relu and y is None:
-        raise ValueError("batchnorm_act_backward_bf16: relu needs y (the forward's output)")
-    need_dres = bool(need_dres and relu)
-    if not (need_dx or need_dres or need_dw):
-        return None, None, None, None
-    L = _lib.load()
-    dev = x.device
-    N, C, H, W = x.shape
-    _check_per_channel("batchnorm_act_backward_bf16", C, dev, weight=weight, mean=mean, invstd=invstd)
-    dx = torch.empty_like(x, memory_format=torch.channels_last) if need_dx else None
-    dres = torch.empty_like(x, memory_format=torch.channels_last) if need_dres else None
-    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    a = _lib.BnGradBf16Args()
-    a.rows, a.channels, a.relu = N * H * W, C, int(bool(relu))
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y, a.dy = p(x), p(y if relu else None), p(dy)
-    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
-    a.dx, a.dresidual, a.dgamma, a.dbeta = p(dx), p(dres), p(dw), p(db)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_grad_workspace_size_bf16(ctypes.byref(a), ctypes.byref(n)),
-               "mcgmil_bn_grad_workspace_size_bf16")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_act_backward_bf16(ctypes.byref(a), stream), "mcgmil_batchnorm_act_backward_bf16")
-    return dx, dres, dw, db
+    return _bn_act_backward(torch.bfloat16, x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw)
 
 
 def bn_act_bf16_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
                    residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """relu?(bn(x) [+ residual]) through the differentiable op torch.ops.mcgmil.bn_act_bf16
     (mcgmil.library); the activation and the residual are made channels-last first if they are not."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    x = x.contiguous(memory_format=torch.channels_last)
-    if residual is not None:
-        residual = residual.contiguous(memory_format=torch.channels_last)
-    return torch.ops.mcgmil.bn_act_bf16(x, bn.weight, bn.bias, residual, float(bn.eps), bool(relu))[0]
+    return _bn_act_op("bn_act_bf16", bn, x, relu, residual)
 
 
 # ---------------------------------------------------------------- fused stem BatchNorm / pool backward
@@ -1351,20 +1236,20 @@ def native_stem_training(flag: bool = True):
         _native_stem_training = before
 
 
-def _pool_grad_geometry(k: int, stride: int, pad: int) -> bool:
-    """The pool geometry of include/mcgmil_pool_grad.h: k in {2, 3}, 1 <= stride <= k, 0 <= pad <= k / 2."""
-    return k in (2, 3) and 1 <= stride <= k and 0 <= pad and 2 * pad <= k
+def _bn_pool_refusal(x: torch.Tensor, bn: nn.Module, pool: nn.Module, dtype: torch.dtype) -> Optional[str]:
+    """The pool's clauses, then those of `_bn_refusal` (the device last)."""
+    pp = _pool_params(pool)
+    if pp is None or not _pool_grad_geometry(*pp):
+        return "pool: a square floor-mode nn.MaxPool2d, dilation 1, kernel 2 or 3, 1 <= stride <= kernel, pad <= kernel / 2"
+    if x.dim() == 4 and min(_out_hw(x.shape[2], x.shape[3], pp[0], pp[0], pp[1], pp[2])) < 1:
+        return "pool: the window is larger than the padded input"
+    return _bn_refusal(x, bn, None, dtype)
 
 
 def bn_pool_untrainable_reason(x: torch.Tensor, bn: nn.Module, pool: nn.Module) -> Optional[str]:
     """Why `bn_pool_trainable` refuses (x, bn, pool), or None when it holds: the pool's clause, then
     those of `bn_untrainable_reason` (the device last)."""
-    pp = _pool_params(pool)
-    if pp is None or not _pool_grad_geometry(*pp):
-        return "pool: a square floor-mode nn.MaxPool2d, dilation 1, kernel 2 or 3, 1 <= stride <= kernel, pad <= kernel / 2"
-    if x.dim() == 4 and min((x.shape[2] + 2 * pp[2] - pp[0]) // pp[1], (x.shape[3] + 2 * pp[2] - pp[0]) // pp[1]) < 0:
-        return "pool: the window is larger than the padded input"
-    return bn_untrainable_reason(x, bn)
+    return _bn_pool_refusal(x, bn, pool, torch.float32)
 
 
 def bn_pool_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, pool: nn.Module) -> bool:
@@ -1375,8 +1260,47 @@ def bn_pool_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, pool: nn.Module) -> b
     return bn_pool_untrainable_reason(x, bn, pool) is None
 
 
-def _pooled_hw(H: int, W: int, k: int, stride: int, pad: int):
-    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+def _bn_pool_backward(dtype: torch.dtype, z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
+    """batchnorm_pool_backward and batchnorm_pool_backward_bf16."""
+    twin = _TWIN[dtype]
+    name = "batchnorm_pool_backward" + twin.suffix
+    _check_rows_c(name, dtype, z)
+    if not _pool_grad_geometry(k, stride, pad):
+        raise ValueError(f"{name} needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
+                         "0 <= pad <= kernel / 2")
+    dev = z.device
+    N, C, H, W = z.shape
+    PH, PW = _out_hw(H, W, k, k, stride, pad)
+    for n, t, dt in (("argmax", argmax, torch.uint8), ("dy", dy, dtype)):
+        if tuple(t.shape) != (N, C, PH, PW) or t.dtype != dt or t.device != dev or \
+                not t.is_contiguous(memory_format=torch.channels_last):
+            raise ValueError(f"{name}: {n} must be a channels-last {dt} {(N, C, PH, PW)} "
+                             "tensor on z's device")
+    if not (need_dz or need_dw):
+        return None, None, None
+    L = _lib.load()
+    _check_per_channel(name, C, dev, weight=weight, mean=mean, invstd=invstd)
+    dz = torch.empty_like(z, memory_format=torch.channels_last) if need_dz else None
+    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
+    a = twin.bn_pool_grad_args()
+    a.batch, a.height, a.width, a.channels = N, H, W, C
+    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
+    a.pooled_height, a.pooled_width = PH, PW
+    a.z, a.argmax, a.dy = _ptr(z), _ptr(argmax), _ptr(dy)
+    a.gamma, a.mean, a.invstd = _ptr(weight), _ptr(mean), _ptr(invstd)
+    a.dz, a.dgamma, a.dbeta = _ptr(dz), _ptr(dw), _ptr(db)
+    size, launch = "mcgmil_bn_pool_grad_workspace_size" + twin.suffix, "mcgmil_batchnorm_pool_backward" + twin.suffix
+    _workspace(getattr(L, size), size, a, dev)
+    _lib.check(getattr(L, launch)(ctypes.byref(a), _stream(dev)), launch)
+    return dz, dw, db
+
+
+def _bn_pool_op(op: str, bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, pool: nn.MaxPool2d) -> torch.Tensor:
+    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
+    k, stride, pad = _pool_params(pool)
+    x = x.contiguous(memory_format=torch.channels_last)
+    return getattr(torch.ops.mcgmil, op)(x, bn.weight, bn.bias, float(bn.eps), bool(relu), k, stride, pad)[0]
 
 
 def batchnorm_pool_stats(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
@@ -1385,37 +1309,7 @@ def batchnorm_pool_stats(z: torch.Tensor, weight: Optional[torch.Tensor], bias: 
     batch statistics of z (fp32, channels-last): mcgmil_batchnorm_pool_train. y is bitwise
     batchnorm_act(..., pool=...); argmax is a channels-last uint8 [N, C, PH, PW] tensor of window
     codes kh * k + kw (255: the ReLU zeroes that gradient). What batchnorm_pool_backward needs."""
-    _check_rows_c("batchnorm_pool_stats", z)
-    if not _pool_grad_geometry(k, stride, pad):
-        raise ValueError("batchnorm_pool_stats needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
-                         "0 <= pad <= kernel / 2")
-    L = _lib.load()
-    dev = z.device
-    N, C, H, W = z.shape
-    PH, PW = _pooled_hw(H, W, k, stride, pad)
-    if PH < 1 or PW < 1:
-        raise ValueError("batchnorm_pool_stats: the pooling window is larger than the padded input")
-    _check_per_channel("batchnorm_pool_stats", C, dev, weight=weight, bias=bias)
-    y = torch.empty((N, C, PH, PW), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
-    argmax = torch.empty((N, C, PH, PW), dtype=torch.uint8, device=dev, memory_format=torch.channels_last)
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_F32
-    a.batch, a.height, a.width = N, H, W
-    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y = p(z), p(y)
-    a.gamma, a.beta = p(weight), p(bias)
-    a.eps, a.relu = float(eps), int(bool(relu))
-    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_pool_train(ctypes.byref(a), p(argmax), stream), "mcgmil_batchnorm_pool_train")
-    return y, mean, invstd, argmax
+    return _bn_stats(torch.float32, "batchnorm_pool_stats", z, weight, bias, None, eps, relu, (k, stride, pad))
 
 
 def batchnorm_pool_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor,
@@ -1424,50 +1318,13 @@ def batchnorm_pool_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Ten
     """(dz, dweight, dbias), None where not needed, of batchnorm_pool_stats given dy
     (mcgmil_batchnorm_pool_backward, include/mcgmil_pool_grad.h). argmax holds the forward's window
     codes; dy is channels-last [N, C, PH, PW]."""
-    _check_rows_c("batchnorm_pool_backward", z)
-    if not _pool_grad_geometry(k, stride, pad):
-        raise ValueError("batchnorm_pool_backward needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
-                         "0 <= pad <= kernel / 2")
-    dev = z.device
-    N, C, H, W = z.shape
-    PH, PW = _pooled_hw(H, W, k, stride, pad)
-    for name, t, dt in (("argmax", argmax, torch.uint8), ("dy", dy, torch.float32)):
-        if tuple(t.shape) != (N, C, PH, PW) or t.dtype != dt or t.device != dev or \
-                not t.is_contiguous(memory_format=torch.channels_last):
-            raise ValueError(f"batchnorm_pool_backward: {name} must be a channels-last {dt} {(N, C, PH, PW)} "
-                             "tensor on z's device")
-    if not (need_dz or need_dw):
-        return None, None, None
-    L = _lib.load()
-    _check_per_channel("batchnorm_pool_backward", C, dev, weight=weight, mean=mean, invstd=invstd)
-    dz = torch.empty_like(z, memory_format=torch.channels_last) if need_dz else None
-    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    a = _lib.BnPoolGradArgs()
-    a.batch, a.height, a.width, a.channels = N, H, W, C
-    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
-    a.pooled_height, a.pooled_width = PH, PW
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.z, a.argmax, a.dy = p(z), p(argmax), p(dy)
-    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
-    a.dz, a.dgamma, a.dbeta = p(dz), p(dw), p(db)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_pool_grad_workspace_size(ctypes.byref(a), ctypes.byref(n)),
-               "mcgmil_bn_pool_grad_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_pool_backward(ctypes.byref(a), stream), "mcgmil_batchnorm_pool_backward")
-    return dz, dw, db
+    return _bn_pool_backward(torch.float32, z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw)
 
 
 def bn_pool_f32_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, pool: nn.MaxPool2d) -> torch.Tensor:
     """pool(relu?(bn(x))) through the differentiable op torch.ops.mcgmil.bn_pool_f32
     (mcgmil.library); the activation is made channels-last first if it is not."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    k, stride, pad = _pool_params(pool)
-    x = x.contiguous(memory_format=torch.channels_last)
-    return torch.ops.mcgmil.bn_pool_f32(x, bn.weight, bn.bias, float(bn.eps), bool(relu), k, stride, pad)[0]
+    return _bn_pool_op("bn_pool_f32", bn, x, relu, pool)
 
 
 # ---------------------------------------------------------------- fused bf16 stem BatchNorm / pool backward
@@ -1494,12 +1351,7 @@ def bn_pool_bf16_untrainable_reason(x: torch.Tensor, bn: nn.Module, pool: nn.Mod
     """Why `bn_pool_bf16_trainable` refuses (x, bn, pool), or None when it holds: the pool's clause
     of `bn_pool_untrainable_reason`, then the clauses of `bn_bf16_untrainable_reason` (the device
     last)."""
-    pp = _pool_params(pool)
-    if pp is None or not _pool_grad_geometry(*pp):
-        return "pool: a square floor-mode nn.MaxPool2d, dilation 1, kernel 2 or 3, 1 <= stride <= kernel, pad <= kernel / 2"
-    if x.dim() == 4 and min((x.shape[2] + 2 * pp[2] - pp[0]) // pp[1], (x.shape[3] + 2 * pp[2] - pp[0]) // pp[1]) < 0:
-        return "pool: the window is larger than the padded input"
-    return bn_bf16_untrainable_reason(x, bn)
+    return _bn_pool_refusal(x, bn, pool, torch.bfloat16)
 
 
 def bn_pool_bf16_trainable(x: torch.Tensor, bn: nn.BatchNorm2d, pool: nn.Module) -> bool:
@@ -1517,38 +1369,7 @@ def batchnorm_pool_stats_bf16(z: torch.Tensor, weight: Optional[torch.Tensor], b
     is a channels-last uint8 [N, C, PH, PW] tensor of window codes kh * k + kw taken on the unrounded
     fp32 activated value (255: the ReLU zeroes that gradient). What batchnorm_pool_backward_bf16
     needs."""
-    _check_rows_c_bf16("batchnorm_pool_stats_bf16", z)
-    if not _pool_grad_geometry(k, stride, pad):
-        raise ValueError("batchnorm_pool_stats_bf16 needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
-                         "0 <= pad <= kernel / 2")
-    L = _lib.load()
-    dev = z.device
-    N, C, H, W = z.shape
-    PH, PW = _pooled_hw(H, W, k, stride, pad)
-    if PH < 1 or PW < 1:
-        raise ValueError("batchnorm_pool_stats_bf16: the pooling window is larger than the padded input")
-    _check_per_channel("batchnorm_pool_stats_bf16", C, dev, weight=weight, bias=bias)
-    y = torch.empty((N, C, PH, PW), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
-    argmax = torch.empty((N, C, PH, PW), dtype=torch.uint8, device=dev, memory_format=torch.channels_last)
-    mean = torch.empty(C, dtype=torch.float32, device=dev)
-    invstd = torch.empty(C, dtype=torch.float32, device=dev)
-    a = _lib.BnArgs()
-    a.rows, a.channels, a.dtype = N * H * W, C, _lib.MCGMIL_BF16
-    a.batch, a.height, a.width = N, H, W
-    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.y = p(z), p(y)
-    a.gamma, a.beta = p(weight), p(bias)
-    a.eps, a.relu = float(eps), int(bool(relu))
-    a.batch_mean, a.batch_invstd = p(mean), p(invstd)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_bn_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_pool_train_bf16(ctypes.byref(a), p(argmax), stream),
-               "mcgmil_batchnorm_pool_train_bf16")
-    return y, mean, invstd, argmax
+    return _bn_stats(torch.bfloat16, "batchnorm_pool_stats", z, weight, bias, None, eps, relu, (k, stride, pad))
 
 
 def batchnorm_pool_backward_bf16(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor,
@@ -1557,50 +1378,13 @@ def batchnorm_pool_backward_bf16(z: torch.Tensor, argmax: torch.Tensor, dy: torc
     """(dz bf16, dweight fp32, dbias fp32), None where not needed, of batchnorm_pool_stats_bf16 given
     dy (mcgmil_batchnorm_pool_backward_bf16, include/mcgmil_pool_grad_bf16.h). argmax holds the
     forward's window codes; dy is channels-last bf16 [N, C, PH, PW]."""
-    _check_rows_c_bf16("batchnorm_pool_backward_bf16", z)
-    if not _pool_grad_geometry(k, stride, pad):
-        raise ValueError("batchnorm_pool_backward_bf16 needs a pool with kernel 2 or 3, 1 <= stride <= kernel and "
-                         "0 <= pad <= kernel / 2")
-    dev = z.device
-    N, C, H, W = z.shape
-    PH, PW = _pooled_hw(H, W, k, stride, pad)
-    for name, t, dt in (("argmax", argmax, torch.uint8), ("dy", dy, torch.bfloat16)):
-        if tuple(t.shape) != (N, C, PH, PW) or t.dtype != dt or t.device != dev or \
-                not t.is_contiguous(memory_format=torch.channels_last):
-            raise ValueError(f"batchnorm_pool_backward_bf16: {name} must be a channels-last {dt} {(N, C, PH, PW)} "
-                             "tensor on z's device")
-    if not (need_dz or need_dw):
-        return None, None, None
-    L = _lib.load()
-    _check_per_channel("batchnorm_pool_backward_bf16", C, dev, weight=weight, mean=mean, invstd=invstd)
-    dz = torch.empty_like(z, memory_format=torch.channels_last) if need_dz else None
-    dw = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    db = torch.empty(C, dtype=torch.float32, device=dev) if need_dw else None
-    a = _lib.BnPoolGradBf16Args()
-    a.batch, a.height, a.width, a.channels = N, H, W, C
-    a.pool_kernel, a.pool_stride, a.pool_pad = k, stride, pad
-    a.pooled_height, a.pooled_width = PH, PW
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.z, a.argmax, a.dy = p(z), p(argmax), p(dy)
-    a.gamma, a.mean, a.invstd = p(weight), p(mean), p(invstd)
-    a.dz, a.dgamma, a.dbeta = p(dz), p(dw), p(db)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_bn_pool_grad_workspace_size_bf16(ctypes.byref(a), ctypes.byref(n)),
-               "mcgmil_bn_pool_grad_workspace_size_bf16")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)          # freed after the launches,
-    a.workspace, a.workspace_bytes = p(ws), n.value                   # stream-ordered
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_batchnorm_pool_backward_bf16(ctypes.byref(a), stream), "mcgmil_batchnorm_pool_backward_bf16")
-    return dz, dw, db
+    return _bn_pool_backward(torch.bfloat16, z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw)
 
 
 def bn_pool_bf16_op(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool, pool: nn.MaxPool2d) -> torch.Tensor:
     """pool(relu?(bn(x))) through the differentiable op torch.ops.mcgmil.bn_pool_bf16
     (mcgmil.library); the activation is made channels-last first if it is not."""
-    from . import library  # noqa: F401  (registers torch.ops.mcgmil.*)
-    k, stride, pad = _pool_params(pool)
-    x = x.contiguous(memory_format=torch.channels_last)
-    return torch.ops.mcgmil.bn_pool_bf16(x, bn.weight, bn.bias, float(bn.eps), bool(relu), k, stride, pad)[0]
+    return _bn_pool_op("bn_pool_bf16", bn, x, relu, pool)
 
 
 def bn_act(bn: nn.BatchNorm2d, x: torch.Tensor, relu: bool,
@@ -1696,9 +1480,7 @@ def packed_stem_weight(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     if wc.dtype not in _DT:
         wc = wc.float()
     packed = torch.empty(n.value, dtype=torch.uint8, device=x.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    _lib.check(L.mcgmil_pack_stem_weights(ctypes.byref(a), ctypes.c_void_p(wc.data_ptr()), _DT[wc.dtype],
-                                          ctypes.c_void_p(packed.data_ptr()), stream),
+    _lib.check(L.mcgmil_pack_stem_weights(ctypes.byref(a), _ptr(wc), _DT[wc.dtype], _ptr(packed), _stream(x.device)),
                "mcgmil_pack_stem_weights")
     conv._mcgmil_stem_packed = (key, packed)
     return packed
@@ -1717,31 +1499,20 @@ def stem(conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, pool: Optional[nn.MaxP
     xb = x.to(torch.bfloat16).contiguous()
     a = _stem_args(conv, xb)
     N, _, H, W = xb.shape
-    OH = (H + 2 * a.pad - a.kernel) // 2 + 1
-    OW = (W + 2 * a.pad - a.kernel) // 2 + 1
-    PH, PW = OH, OW
+    PH, PW = _out_hw(H, W, a.kernel, a.kernel, 2, a.pad)
     if pool is not None:
         k, st, pd = _pool_params(pool)
         a.pool_kernel, a.pool_stride, a.pool_pad = k, st, pd
-        PH, PW = (OH + 2 * pd - k) // st + 1, (OW + 2 * pd - k) // st + 1
-    use_batch = bn.training or bn.running_mean is None or bn.running_var is None
-    gamma = _f32(bn.weight, dev) if bn.affine else None
-    beta = _f32(bn.bias, dev) if bn.affine else None
-    rmean = None if use_batch else _f32(bn.running_mean, dev)
-    rvar = None if use_batch else _f32(bn.running_var, dev)
+        PH, PW = _out_hw(PH, PW, k, k, st, pd)
+    _, gamma, beta, rmean, rvar = _bn_tensors(bn, dev)
     w = packed_stem_weight(conv, xb)
     y = torch.empty((N, 64, PH, PW), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
-    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    a.x, a.w, a.y = p(xb), p(w), p(y)
-    a.gamma, a.beta, a.running_mean, a.running_var = p(gamma), p(beta), p(rmean), p(rvar)
+    a.x, a.w, a.y = _ptr(xb), _ptr(w), _ptr(y)
+    a.gamma, a.beta, a.running_mean, a.running_var = _ptr(gamma), _ptr(beta), _ptr(rmean), _ptr(rvar)
     a.eps, a.relu = float(bn.eps), int(bool(relu))
     a.flags = int(flags)
-    n = ctypes.c_size_t()
-    _lib.check(L.mcgmil_stem_workspace_size(ctypes.byref(a), ctypes.byref(n)), "mcgmil_stem_workspace_size")
-    ws = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    a.workspace, a.workspace_bytes = p(ws), n.value
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(L.mcgmil_stem_forward(ctypes.byref(a), stream), "mcgmil_stem_forward")
+    _workspace(L.mcgmil_stem_workspace_size, "mcgmil_stem_workspace_size", a, dev)
+    _lib.check(L.mcgmil_stem_forward(ctypes.byref(a), _stream(dev)), "mcgmil_stem_forward")
     return y
 
 
@@ -1772,10 +1543,6 @@ class DeferredBN(NamedTuple):
 
     def materialise(self) -> torch.Tensor:
         return batchnorm_act(self.y, self.bn, self.relu, partials=self.partials)
-
-
-def _use_batch(bn: nn.BatchNorm2d) -> bool:
-    return bn.training or bn.running_mean is None or bn.running_var is None
 
 
 def conv_bn_act(conv: nn.Module, bn: nn.Module, x, relu: bool, residual=None,

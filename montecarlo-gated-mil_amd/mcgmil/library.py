@@ -101,8 +101,13 @@ batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the 
 implementations below only derive output shapes, and the real ones run the gfx950 kernels
 through the C ABI. There is no CPU kernel: called with CPU tensors they raise. `seed` is the
 64-bit Philox key as a signed int64 (the schema's int); it is reinterpreted as unsigned.
+
+Each family of backbone ops (the convolutions, bn_act, bn_pool) is written once, as a function
+that defines and registers an op, its fake, its backward op, that one's fake and the autograd
+formula for one dtype; what differs between the members is its arguments. The `features` functions
+are named, not passed, and looked up on every call.
 """
-from typing import Optional, Tuple
+from typing import Callable, Optional, Tuple
 
 import torch
 
@@ -205,410 +210,238 @@ def _mcdo_forward_stats_fake(H, bag_offsets, Wv, bv, Wu, bu, wa, ba, wk, T, p_fe
             H.new_empty((C * R,), dtype=f), H.new_empty((B, C), dtype=f))
 
 
-def _conv_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
-    """(shim, x channels-last) for the fp32 convolution entry points, or ValueError."""
-    x = x.detach().contiguous(memory_format=torch.channels_last)
-    conv = features._ConvShim(weight, stride, pad)
-    if not features.conv32_trainable(conv, x):
-        raise ValueError("mcgmil::conv2d_f32 needs a CUDA fp32 activation and weight with kernel 1..7, "
-                         "stride 1 or 2, pad < kernel, in_channels % 16 == 0 and out_channels % 64 == 0 "
-                         "(features.conv32_trainable)")
-    return conv, x
-
-
-def _conv_out_hw(x, weight, stride, pad):
-    return ((x.shape[2] + 2 * pad - weight.shape[2]) // stride + 1,
-            (x.shape[3] + 2 * pad - weight.shape[3]) // stride + 1)
-
-
-@torch.library.custom_op("mcgmil::conv2d_f32", mutates_args=())
-def conv2d_f32(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-    with torch.no_grad():
-        conv, xc = _conv_shim(x, weight, stride, pad)
-        return features.conv2d_f32(conv, xc)
-
-
-@conv2d_f32.register_fake
-def _conv2d_f32_fake(x, weight, stride, pad):
-    oh, ow = _conv_out_hw(x, weight, stride, pad)
-    return torch.empty((x.shape[0], weight.shape[0], oh, ow), dtype=torch.float32, device=x.device,
-                       memory_format=torch.channels_last)
-
-
-@torch.library.custom_op("mcgmil::conv2d_f32_backward", mutates_args=())
-def conv2d_f32_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
-                        need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        conv, xc = _conv_shim(x, weight, stride, pad)
-        dx, dw = features.conv2d_f32_backward(conv, xc, dy.detach(), need_dx, need_dw)
-    return (dx if need_dx else x.new_empty((0,))), (dw if need_dw else weight.new_empty((0,)))
-
-
-@conv2d_f32_backward.register_fake
-def _conv2d_f32_backward_fake(x, weight, dy, stride, pad, need_dx, need_dw):
-    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last) \
-        if need_dx else x.new_empty((0,))
-    dw = weight.new_empty(weight.shape, dtype=torch.float32) if need_dw else weight.new_empty((0,))
-    return dx, dw
-
-
-def _conv_setup_context(ctx, inputs, output):
-    x, weight, stride, pad = inputs
-    ctx.save_for_backward(x, weight)
-    ctx.geometry = (stride, pad)
-
-
-def _conv_backward(ctx, dy):
-    x, weight = ctx.saved_tensors
-    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    dx, dw = torch.ops.mcgmil.conv2d_f32_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
-    return dx if need_dx else None, dw if need_dw else None, None, None
-
-
-conv2d_f32.register_autograd(_conv_backward, setup_context=_conv_setup_context)
+# ---------------------------------------------------------------- the backbone's training ops
+_CL = torch.channels_last
 
 
 def _channels_last(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().contiguous(memory_format=torch.channels_last)
+    return t.detach().contiguous(memory_format=_CL)
 
 
-@torch.library.custom_op("mcgmil::bn_act_f32", mutates_args=())
-def bn_act_f32(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-               residual: Optional[torch.Tensor], eps: float, relu: bool
-               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
-        return features.batchnorm_act_stats(_channels_last(x), f(weight), f(bias),
-                                            None if residual is None else _channels_last(residual), eps, relu)
+def _plain(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if t is None else t.detach().contiguous()
 
 
-@bn_act_f32.register_fake
-def _bn_act_f32_fake(x, weight, bias, residual, eps, relu):
-    y = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    return y, x.new_empty((x.shape[1],), dtype=torch.float32), x.new_empty((x.shape[1],), dtype=torch.float32)
+def _or_empty(t: Optional[torch.Tensor], like: torch.Tensor) -> torch.Tensor:
+    """A gradient that was not needed comes back as an empty tensor of `like`'s dtype and device."""
+    return like.new_empty((0,)) if t is None else t
 
 
-@torch.library.custom_op("mcgmil::bn_act_f32_backward", mutates_args=())
-def bn_act_f32_backward(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
-                        mean: torch.Tensor, invstd: torch.Tensor, relu: bool, need_dx: bool, need_dres: bool,
-                        need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        dx, dres, dw, db = features.batchnorm_act_backward(
-            _channels_last(x), _channels_last(y) if relu else None, _channels_last(dy),
-            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
-            invstd.detach().contiguous(), relu, need_dx, need_dres, need_dw)
-    e = lambda t: x.new_empty((0,)) if t is None else t  # noqa: E731
-    return e(dx), e(dres), e(dw), e(db)
+def _empty_cl(shape, dtype, like: torch.Tensor, need: bool = True) -> torch.Tensor:
+    return torch.empty(shape, dtype=dtype, device=like.device, memory_format=_CL) if need else like.new_empty((0,))
 
 
-@bn_act_f32_backward.register_fake
-def _bn_act_f32_backward_fake(x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
-    full = lambda need: torch.empty(x.shape, dtype=torch.float32, device=x.device,  # noqa: E731
-                                    memory_format=torch.channels_last) if need else x.new_empty((0,))
-    vec = lambda: x.new_empty((x.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
-    return full(need_dx), full(need_dres and relu), vec(), vec()
+def _conv_family(name: str, dtype: torch.dtype, refusal: Callable, forward: str, backward: Callable,
+                 cast_dy: bool, dw_dtype: Optional[torch.dtype]):
+    """Register mcgmil::<name> and mcgmil::<name>_backward, a convolution's op of `dtype`.
+    refusal(shim, x): why the op does not take them (the ValueError's text), or None; forward: the
+    name of the features function; backward(shim, x, dy, need_dx, need_dw) -> (dx | None, dw | None);
+    cast_dy: dy is cast to `dtype` first; dw_dtype: the fake dw's dtype (None: the weight's)."""
+    def shim(x, weight, stride, pad):
+        x = _channels_last(x)
+        conv = features._ConvShim(weight, stride, pad)
+        why = refusal(conv, x)
+        if why is not None:
+            raise ValueError(why)
+        return conv, x
+
+    @torch.library.custom_op(f"mcgmil::{name}", mutates_args=())
+    def op(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
+        with torch.no_grad():
+            conv, xc = shim(x, weight, stride, pad)
+            return getattr(features, forward)(conv, xc)
+
+    @op.register_fake
+    def _(x, weight, stride, pad):
+        oh, ow = ((x.shape[i] + 2 * pad - weight.shape[i]) // stride + 1 for i in (2, 3))
+        return _empty_cl((x.shape[0], weight.shape[0], oh, ow), dtype, x)
+
+    @torch.library.custom_op(f"mcgmil::{name}_backward", mutates_args=())
+    def op_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
+                    need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        with torch.no_grad():
+            conv, xc = shim(x, weight, stride, pad)
+            dy = dy.detach()
+            dx, dw = backward(conv, xc, dy.to(dtype) if cast_dy else dy, need_dx, need_dw)
+        return _or_empty(dx if need_dx else None, x), _or_empty(dw if need_dw else None, weight)
+
+    @op_backward.register_fake
+    def _(x, weight, dy, stride, pad, need_dx, need_dw):
+        dw = weight.new_empty(weight.shape, dtype=dw_dtype) if need_dw else weight.new_empty((0,))
+        return _empty_cl(x.shape, dtype, x, need_dx), dw
+
+    def setup_context(ctx, inputs, output):
+        x, weight, stride, pad = inputs
+        ctx.save_for_backward(x, weight)
+        ctx.geometry = (stride, pad)
+
+    def formula(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx, dw = getattr(torch.ops.mcgmil, name + "_backward")(x, weight, dy, *ctx.geometry, need_dx, need_dw)
+        return dx if need_dx else None, dw if need_dw else None, None, None
+
+    op.register_autograd(formula, setup_context=setup_context)
+    return op, op_backward
 
 
-def _bn_setup_context(ctx, inputs, output):
-    x, weight, bias, residual, eps, relu = inputs
-    y, mean, invstd = output
-    ctx.relu, ctx.has_weight = relu, weight is not None
-    # y is needed for the ReLU mask only
-    ctx.save_for_backward(x, mean, invstd, *((weight,) if weight is not None else ()), *((y,) if relu else ()))
-    ctx.set_materialize_grads(False)
+def _conv32_refusal(conv, x):
+    if not features.conv32_trainable(conv, x):
+        return ("mcgmil::conv2d_f32 needs a CUDA fp32 activation and weight with kernel 1..7, "
+                "stride 1 or 2, pad < kernel, in_channels % 16 == 0 and out_channels % 64 == 0 "
+                "(features.conv32_trainable)")
 
 
-def _bn_backward(ctx, dy, dmean, dinvstd):
-    # dmean / dinvstd: mean and invstd are by-products for the backward, not differentiable outputs
-    if dy is None:
-        return (None,) * 6
-    x, mean, invstd, *rest = ctx.saved_tensors
-    weight = rest.pop(0) if ctx.has_weight else None
-    y = rest.pop(0) if ctx.relu else x.new_empty((0,))
-    need = ctx.needs_input_grad
-    need_dx, need_dw, need_dres = need[0], need[1] or need[2], need[3]
-    dx, dres, dw, db = torch.ops.mcgmil.bn_act_f32_backward(x, y, dy, weight, mean, invstd, ctx.relu, need_dx,
-                                                            need_dres and ctx.relu, need_dw)
-    if need_dres and not ctx.relu:
-        dres = dy
-    return (dx if need_dx else None, dw if need[1] else None, db if need[2] else None,
-            dres if need_dres else None, None, None)
+def _named_refusal(name: str, reason: str, trainable: str) -> Callable:
+    def refusal(conv, x):
+        why = getattr(features, reason)(conv, x)
+        return None if why is None else f"mcgmil::{name}: {why} (features.{trainable})"
+    return refusal
 
 
-bn_act_f32.register_autograd(_bn_backward, setup_context=_bn_setup_context)
-
-
-@torch.library.custom_op("mcgmil::bn_act_bf16", mutates_args=())
-def bn_act_bf16(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
-                residual: Optional[torch.Tensor], eps: float, relu: bool
-                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
-        return features.batchnorm_act_stats_bf16(_channels_last(x), f(weight), f(bias),
-                                                 None if residual is None else _channels_last(residual), eps, relu)
-
-
-@bn_act_bf16.register_fake
-def _bn_act_bf16_fake(x, weight, bias, residual, eps, relu):
-    y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    return y, x.new_empty((x.shape[1],), dtype=torch.float32), x.new_empty((x.shape[1],), dtype=torch.float32)
-
-
-@torch.library.custom_op("mcgmil::bn_act_bf16_backward", mutates_args=())
-def bn_act_bf16_backward(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
-                         mean: torch.Tensor, invstd: torch.Tensor, relu: bool, need_dx: bool, need_dres: bool,
-                         need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        dx, dres, dw, db = features.batchnorm_act_backward_bf16(
-            _channels_last(x), _channels_last(y) if relu else None, _channels_last(dy.to(torch.bfloat16)),
-            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
-            invstd.detach().contiguous(), relu, need_dx, need_dres, need_dw)
-    e = lambda t, like: like.new_empty((0,)) if t is None else t  # noqa: E731
-    return e(dx, x), e(dres, x), e(dw, mean), e(db, mean)
-
-
-@bn_act_bf16_backward.register_fake
-def _bn_act_bf16_backward_fake(x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
-    full = lambda need: torch.empty(x.shape, dtype=torch.bfloat16, device=x.device,  # noqa: E731
-                                    memory_format=torch.channels_last) if need else x.new_empty((0,))
-    vec = lambda: mean.new_empty((x.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
-    return full(need_dx), full(need_dres and relu), vec(), vec()
-
-
-def _bn_bf16_backward(ctx, dy, dmean, dinvstd):
-    # as _bn_backward: mean and invstd are by-products for the backward, not differentiable outputs
-    if dy is None:
-        return (None,) * 6
-    x, mean, invstd, *rest = ctx.saved_tensors
-    weight = rest.pop(0) if ctx.has_weight else None
-    y = rest.pop(0) if ctx.relu else x.new_empty((0,))
-    need = ctx.needs_input_grad
-    need_dx, need_dw, need_dres = need[0], need[1] or need[2], need[3]
-    dx, dres, dw, db = torch.ops.mcgmil.bn_act_bf16_backward(x, y, dy, weight, mean, invstd, ctx.relu, need_dx,
-                                                             need_dres and ctx.relu, need_dw)
-    if need_dres and not ctx.relu:
-        dres = dy
-    return (dx if need_dx else None, dw if need[1] else None, db if need[2] else None,
-            dres if need_dres else None, None, None)
-
-
-bn_act_bf16.register_autograd(_bn_bf16_backward, setup_context=_bn_setup_context)
-
-
-@torch.library.custom_op("mcgmil::bn_pool_f32", mutates_args=())
-def bn_pool_f32(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
-                relu: bool, k: int, stride: int, pad: int
-                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
-        return features.batchnorm_pool_stats(_channels_last(z), f(weight), f(bias), eps, relu, k, stride, pad)
-
-
-def _pooled_shape(z, k, stride, pad):
-    return (z.shape[0], z.shape[1], (z.shape[2] + 2 * pad - k) // stride + 1, (z.shape[3] + 2 * pad - k) // stride + 1)
-
-
-@bn_pool_f32.register_fake
-def _bn_pool_f32_fake(z, weight, bias, eps, relu, k, stride, pad):
-    shape = _pooled_shape(z, k, stride, pad)
-    y = torch.empty(shape, dtype=torch.float32, device=z.device, memory_format=torch.channels_last)
-    argmax = torch.empty(shape, dtype=torch.uint8, device=z.device, memory_format=torch.channels_last)
-    return (y, z.new_empty((z.shape[1],), dtype=torch.float32), z.new_empty((z.shape[1],), dtype=torch.float32),
-            argmax)
-
-
-@torch.library.custom_op("mcgmil::bn_pool_f32_backward", mutates_args=())
-def bn_pool_f32_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
-                         mean: torch.Tensor, invstd: torch.Tensor, k: int, stride: int, pad: int, need_dz: bool,
-                         need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        dz, dw, db = features.batchnorm_pool_backward(
-            _channels_last(z), _channels_last(argmax), _channels_last(dy),
-            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
-            invstd.detach().contiguous(), k, stride, pad, need_dz, need_dw)
-    e = lambda t: z.new_empty((0,)) if t is None else t  # noqa: E731
-    return e(dz), e(dw), e(db)
-
-
-@bn_pool_f32_backward.register_fake
-def _bn_pool_f32_backward_fake(z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
-    dz = torch.empty(z.shape, dtype=torch.float32, device=z.device, memory_format=torch.channels_last) \
-        if need_dz else z.new_empty((0,))
-    vec = lambda: z.new_empty((z.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
-    return dz, vec(), vec()
-
-
-def _bn_pool_setup_context(ctx, inputs, output):
-    z, weight, bias, eps, relu, k, stride, pad = inputs
-    y, mean, invstd, argmax = output
-    ctx.geometry, ctx.has_weight = (k, stride, pad), weight is not None
-    # neither y nor the activation: the codes say where each pooled gradient goes
-    ctx.save_for_backward(z, argmax, mean, invstd, *((weight,) if weight is not None else ()))
-    ctx.set_materialize_grads(False)
-
-
-def _bn_pool_backward(ctx, dy, dmean, dinvstd, dargmax):
-    # dmean / dinvstd / dargmax: by-products for the backward, not differentiable outputs
-    if dy is None:
-        return (None,) * 8
-    z, argmax, mean, invstd, *rest = ctx.saved_tensors
-    weight = rest[0] if ctx.has_weight else None
-    need = ctx.needs_input_grad
-    need_dz, need_dw = need[0], need[1] or need[2]
-    dz, dw, db = torch.ops.mcgmil.bn_pool_f32_backward(z, argmax, dy, weight, mean, invstd, *ctx.geometry,
-                                                       need_dz, need_dw)
-    return (dz if need_dz else None, dw if need[1] else None, db if need[2] else None) + (None,) * 5
-
-
-bn_pool_f32.register_autograd(_bn_pool_backward, setup_context=_bn_pool_setup_context)
-
-
-@torch.library.custom_op("mcgmil::bn_pool_bf16", mutates_args=())
-def bn_pool_bf16(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
-                 relu: bool, k: int, stride: int, pad: int
-                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        f = lambda t: None if t is None else t.detach().contiguous()  # noqa: E731
-        return features.batchnorm_pool_stats_bf16(_channels_last(z), f(weight), f(bias), eps, relu, k, stride, pad)
-
-
-@bn_pool_bf16.register_fake
-def _bn_pool_bf16_fake(z, weight, bias, eps, relu, k, stride, pad):
-    shape = _pooled_shape(z, k, stride, pad)
-    y = torch.empty(shape, dtype=torch.bfloat16, device=z.device, memory_format=torch.channels_last)
-    argmax = torch.empty(shape, dtype=torch.uint8, device=z.device, memory_format=torch.channels_last)
-    return (y, z.new_empty((z.shape[1],), dtype=torch.float32), z.new_empty((z.shape[1],), dtype=torch.float32),
-            argmax)
-
-
-@torch.library.custom_op("mcgmil::bn_pool_bf16_backward", mutates_args=())
-def bn_pool_bf16_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
-                          mean: torch.Tensor, invstd: torch.Tensor, k: int, stride: int, pad: int, need_dz: bool,
-                          need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        dz, dw, db = features.batchnorm_pool_backward_bf16(
-            _channels_last(z), _channels_last(argmax), _channels_last(dy.to(torch.bfloat16)),
-            None if weight is None else weight.detach().contiguous(), mean.detach().contiguous(),
-            invstd.detach().contiguous(), k, stride, pad, need_dz, need_dw)
-    e = lambda t, like: like.new_empty((0,)) if t is None else t  # noqa: E731
-    return e(dz, z), e(dw, mean), e(db, mean)
-
-
-@bn_pool_bf16_backward.register_fake
-def _bn_pool_bf16_backward_fake(z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
-    dz = torch.empty(z.shape, dtype=torch.bfloat16, device=z.device, memory_format=torch.channels_last) \
-        if need_dz else z.new_empty((0,))
-    vec = lambda: mean.new_empty((z.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
-    return dz, vec(), vec()
-
-
-def _bn_pool_bf16_backward(ctx, dy, dmean, dinvstd, dargmax):
-    # as _bn_pool_backward: the saved tensors are z, the codes, mean, invstd and weight alone
-    if dy is None:
-        return (None,) * 8
-    z, argmax, mean, invstd, *rest = ctx.saved_tensors
-    weight = rest[0] if ctx.has_weight else None
-    need = ctx.needs_input_grad
-    need_dz, need_dw = need[0], need[1] or need[2]
-    dz, dw, db = torch.ops.mcgmil.bn_pool_bf16_backward(z, argmax, dy, weight, mean, invstd, *ctx.geometry,
-                                                        need_dz, need_dw)
-    return (dz if need_dz else None, dw if need[1] else None, db if need[2] else None) + (None,) * 5
-
-
-bn_pool_bf16.register_autograd(_bn_pool_bf16_backward, setup_context=_bn_pool_setup_context)
-
-
-def _stem_conv_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
-    """(shim, x channels-last) for the stem convolution's entry points, or ValueError."""
-    x = x.detach().contiguous(memory_format=torch.channels_last)
-    conv = features._ConvShim(weight, stride, pad)
-    reason = features.stem_conv_untrainable_reason(conv, x)
-    if reason is not None:
-        raise ValueError(f"mcgmil::stem_conv_f32: {reason} (features.stem_conv_trainable)")
-    return conv, x
-
-
-@torch.library.custom_op("mcgmil::stem_conv_f32", mutates_args=())
-def stem_conv_f32(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-    with torch.no_grad():
-        conv, xc = _stem_conv_shim(x, weight, stride, pad)
-        return features.conv2d_f32(conv, xc)
-
-
-stem_conv_f32.register_fake(_conv2d_f32_fake)
-
-
-@torch.library.custom_op("mcgmil::stem_conv_f32_backward", mutates_args=())
-def stem_conv_f32_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
-                           need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        conv, xc = _stem_conv_shim(x, weight, stride, pad)
-        dy = dy.detach().contiguous(memory_format=torch.channels_last)
-        dw = features.conv2d_f32_stem_wgrad(conv, xc, dy) if need_dw else weight.new_empty((0,))
-        # no native data gradient: the model never asks for one (the instances do not require grad)
-        dx = features._aten_conv_backward(conv, xc, dy, True, False)[0] if need_dx else x.new_empty((0,))
+def _stem_conv_grads(conv, x, dy, need_dx, need_dw):
+    dy = dy.contiguous(memory_format=_CL)
+    dw = features.conv2d_f32_stem_wgrad(conv, x, dy) if need_dw else None
+    # no native data gradient: the model never asks for one (the instances do not require grad)
+    dx = features._aten_conv_backward(conv, x, dy, True, False)[0] if need_dx else None
     return dx, dw
 
 
-stem_conv_f32_backward.register_fake(_conv2d_f32_backward_fake)
+conv2d_f32, conv2d_f32_backward = _conv_family(
+    "conv2d_f32", torch.float32, _conv32_refusal, "conv2d_f32",
+    lambda *a: features.conv2d_f32_backward(*a), cast_dy=False, dw_dtype=torch.float32)
+stem_conv_f32, stem_conv_f32_backward = _conv_family(
+    "stem_conv_f32", torch.float32, _named_refusal("stem_conv_f32", "stem_conv_untrainable_reason", "stem_conv_trainable"),
+    "conv2d_f32", _stem_conv_grads, cast_dy=False, dw_dtype=torch.float32)
+conv2d_bf16, conv2d_bf16_backward = _conv_family(
+    "conv2d_bf16", torch.bfloat16, _named_refusal("conv2d_bf16", "conv_bf16_untrainable_reason", "conv_bf16_trainable"),
+    "conv2d_bf16", lambda *a: features.conv2d_bf16_backward(*a), cast_dy=True, dw_dtype=None)
 
 
-def _stem_conv_backward(ctx, dy):
-    x, weight = ctx.saved_tensors
-    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    dx, dw = torch.ops.mcgmil.stem_conv_f32_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
-    return dx if need_dx else None, dw if need_dw else None, None, None
+def _bn_act_family(name: str, dtype: torch.dtype, forward: str, backward: str, mixed: bool):
+    """Register mcgmil::<name> and mcgmil::<name>_backward, the fused BatchNorm (+ add) (+ ReLU)
+    of `dtype`. forward, backward: the names of the features functions; mixed: the bf16 twin,
+    whose dy is cast to `dtype` first and whose placeholders for dweight and dbias (fp32) take
+    their dtype from mean; those for dx and dres, and all of the fp32 op's, take it from x."""
+    @torch.library.custom_op(f"mcgmil::{name}", mutates_args=())
+    def op(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor],
+           residual: Optional[torch.Tensor], eps: float, relu: bool
+           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        with torch.no_grad():
+            return getattr(features, forward)(_channels_last(x), _plain(weight), _plain(bias),
+                                              None if residual is None else _channels_last(residual), eps, relu)
+
+    @op.register_fake
+    def _(x, weight, bias, residual, eps, relu):
+        return (_empty_cl(x.shape, dtype, x), x.new_empty((x.shape[1],), dtype=torch.float32),
+                x.new_empty((x.shape[1],), dtype=torch.float32))
+
+    @torch.library.custom_op(f"mcgmil::{name}_backward", mutates_args=())
+    def op_backward(x: torch.Tensor, y: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                    mean: torch.Tensor, invstd: torch.Tensor, relu: bool, need_dx: bool, need_dres: bool,
+                    need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        with torch.no_grad():
+            dx, dres, dw, db = getattr(features, backward)(
+                _channels_last(x), _channels_last(y) if relu else None, _channels_last(dy.to(dtype) if mixed else dy),
+                _plain(weight), _plain(mean), _plain(invstd), relu, need_dx, need_dres, need_dw)
+        return _or_empty(dx, x), _or_empty(dres, x), _or_empty(dw, mean if mixed else x), _or_empty(db, mean if mixed else x)
+
+    @op_backward.register_fake
+    def _(x, y, dy, weight, mean, invstd, relu, need_dx, need_dres, need_dw):
+        vec = lambda: (mean if mixed else x).new_empty((x.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+        return _empty_cl(x.shape, dtype, x, need_dx), _empty_cl(x.shape, dtype, x, need_dres and relu), vec(), vec()
+
+    def setup_context(ctx, inputs, output):
+        x, weight, bias, residual, eps, relu = inputs
+        y, mean, invstd = output
+        ctx.relu, ctx.has_weight = relu, weight is not None
+        # y is needed for the ReLU mask only
+        ctx.save_for_backward(x, mean, invstd, *((weight,) if weight is not None else ()), *((y,) if relu else ()))
+        ctx.set_materialize_grads(False)
+
+    def formula(ctx, dy, dmean, dinvstd):
+        # dmean / dinvstd: mean and invstd are by-products for the backward, not differentiable outputs
+        if dy is None:
+            return (None,) * 6
+        x, mean, invstd, *rest = ctx.saved_tensors
+        weight = rest.pop(0) if ctx.has_weight else None
+        y = rest.pop(0) if ctx.relu else x.new_empty((0,))
+        need = ctx.needs_input_grad
+        need_dx, need_dw, need_dres = need[0], need[1] or need[2], need[3]
+        dx, dres, dw, db = getattr(torch.ops.mcgmil, name + "_backward")(
+            x, y, dy, weight, mean, invstd, ctx.relu, need_dx, need_dres and ctx.relu, need_dw)
+        if need_dres and not ctx.relu:
+            dres = dy
+        return (dx if need_dx else None, dw if need[1] else None, db if need[2] else None,
+                dres if need_dres else None, None, None)
+
+    op.register_autograd(formula, setup_context=setup_context)
+    return op, op_backward
 
 
-stem_conv_f32.register_autograd(_stem_conv_backward, setup_context=_conv_setup_context)
+bn_act_f32, bn_act_f32_backward = _bn_act_family(
+    "bn_act_f32", torch.float32, "batchnorm_act_stats", "batchnorm_act_backward", mixed=False)
+bn_act_bf16, bn_act_bf16_backward = _bn_act_family(
+    "bn_act_bf16", torch.bfloat16, "batchnorm_act_stats_bf16", "batchnorm_act_backward_bf16", mixed=True)
 
 
-def _conv_bf16_shim(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int):
-    """(shim, x channels-last) for the bf16 convolution's entry points, or ValueError."""
-    x = x.detach().contiguous(memory_format=torch.channels_last)
-    conv = features._ConvShim(weight, stride, pad)
-    reason = features.conv_bf16_untrainable_reason(conv, x)
-    if reason is not None:
-        raise ValueError(f"mcgmil::conv2d_bf16: {reason} (features.conv_bf16_trainable)")
-    return conv, x
+def _bn_pool_family(name: str, dtype: torch.dtype, forward: str, backward: str, mixed: bool):
+    """Register mcgmil::<name> and mcgmil::<name>_backward, the stem's fused BatchNorm (+ ReLU) +
+    max-pool of `dtype`; the arguments as _bn_act_family's. The placeholder for dz takes its dtype
+    from z."""
+    @torch.library.custom_op(f"mcgmil::{name}", mutates_args=())
+    def op(z: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], eps: float,
+           relu: bool, k: int, stride: int, pad: int
+           ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        with torch.no_grad():
+            return getattr(features, forward)(_channels_last(z), _plain(weight), _plain(bias), eps, relu, k, stride, pad)
+
+    @op.register_fake
+    def _(z, weight, bias, eps, relu, k, stride, pad):
+        shape = (z.shape[0], z.shape[1], (z.shape[2] + 2 * pad - k) // stride + 1, (z.shape[3] + 2 * pad - k) // stride + 1)
+        return (_empty_cl(shape, dtype, z), z.new_empty((z.shape[1],), dtype=torch.float32),
+                z.new_empty((z.shape[1],), dtype=torch.float32), _empty_cl(shape, torch.uint8, z))
+
+    @torch.library.custom_op(f"mcgmil::{name}_backward", mutates_args=())
+    def op_backward(z: torch.Tensor, argmax: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Tensor],
+                    mean: torch.Tensor, invstd: torch.Tensor, k: int, stride: int, pad: int, need_dz: bool,
+                    need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        with torch.no_grad():
+            dz, dw, db = getattr(features, backward)(
+                _channels_last(z), _channels_last(argmax), _channels_last(dy.to(dtype) if mixed else dy),
+                _plain(weight), _plain(mean), _plain(invstd), k, stride, pad, need_dz, need_dw)
+        return _or_empty(dz, z), _or_empty(dw, mean if mixed else z), _or_empty(db, mean if mixed else z)
+
+    @op_backward.register_fake
+    def _(z, argmax, dy, weight, mean, invstd, k, stride, pad, need_dz, need_dw):
+        vec = lambda: (mean if mixed else z).new_empty((z.shape[1],) if need_dw else (0,), dtype=torch.float32)  # noqa: E731
+        return _empty_cl(z.shape, dtype, z, need_dz), vec(), vec()
+
+    def setup_context(ctx, inputs, output):
+        z, weight, bias, eps, relu, k, stride, pad = inputs
+        y, mean, invstd, argmax = output
+        ctx.geometry, ctx.has_weight = (k, stride, pad), weight is not None
+        # neither y nor the activation: the codes say where each pooled gradient goes
+        ctx.save_for_backward(z, argmax, mean, invstd, *((weight,) if weight is not None else ()))
+        ctx.set_materialize_grads(False)
+
+    def formula(ctx, dy, dmean, dinvstd, dargmax):
+        # dmean / dinvstd / dargmax: by-products for the backward, not differentiable outputs
+        if dy is None:
+            return (None,) * 8
+        z, argmax, mean, invstd, *rest = ctx.saved_tensors
+        weight = rest[0] if ctx.has_weight else None
+        need = ctx.needs_input_grad
+        need_dz, need_dw = need[0], need[1] or need[2]
+        dz, dw, db = getattr(torch.ops.mcgmil, name + "_backward")(z, argmax, dy, weight, mean, invstd, *ctx.geometry,
+                                                                  need_dz, need_dw)
+        return (dz if need_dz else None, dw if need[1] else None, db if need[2] else None) + (None,) * 5
+
+    op.register_autograd(formula, setup_context=setup_context)
+    return op, op_backward
 
 
-@torch.library.custom_op("mcgmil::conv2d_bf16", mutates_args=())
-def conv2d_bf16(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-    with torch.no_grad():
-        conv, xc = _conv_bf16_shim(x, weight, stride, pad)
-        return features.conv2d_bf16(conv, xc)
-
-
-@conv2d_bf16.register_fake
-def _conv2d_bf16_fake(x, weight, stride, pad):
-    oh, ow = _conv_out_hw(x, weight, stride, pad)
-    return torch.empty((x.shape[0], weight.shape[0], oh, ow), dtype=torch.bfloat16, device=x.device,
-                       memory_format=torch.channels_last)
-
-
-@torch.library.custom_op("mcgmil::conv2d_bf16_backward", mutates_args=())
-def conv2d_bf16_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
-                         need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    with torch.no_grad():
-        conv, xc = _conv_bf16_shim(x, weight, stride, pad)
-        dx, dw = features.conv2d_bf16_backward(conv, xc, dy.detach().to(torch.bfloat16), need_dx, need_dw)
-    return (dx if need_dx else x.new_empty((0,))), (dw if need_dw else weight.new_empty((0,)))
-
-
-@conv2d_bf16_backward.register_fake
-def _conv2d_bf16_backward_fake(x, weight, dy, stride, pad, need_dx, need_dw):
-    dx = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last) \
-        if need_dx else x.new_empty((0,))
-    dw = weight.new_empty(weight.shape) if need_dw else weight.new_empty((0,))
-    return dx, dw
-
-
-def _conv_bf16_backward(ctx, dy):
-    x, weight = ctx.saved_tensors
-    need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-    dx, dw = torch.ops.mcgmil.conv2d_bf16_backward(x, weight, dy, *ctx.geometry, need_dx, need_dw)
-    return dx if need_dx else None, dw if need_dw else None, None, None
-
-
-conv2d_bf16.register_autograd(_conv_bf16_backward, setup_context=_conv_setup_context)
+bn_pool_f32, bn_pool_f32_backward = _bn_pool_family(
+    "bn_pool_f32", torch.float32, "batchnorm_pool_stats", "batchnorm_pool_backward", mixed=False)
+bn_pool_bf16, bn_pool_bf16_backward = _bn_pool_family(
+    "bn_pool_bf16", torch.bfloat16, "batchnorm_pool_stats_bf16", "batchnorm_pool_backward_bf16", mixed=True)
