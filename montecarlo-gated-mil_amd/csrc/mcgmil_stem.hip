@@ -33,6 +33,7 @@
 #include <string>
 
 #include "../../include/mcgmil_features.h"
+#include "../../include/mcgmil_stem_grad_bf16.h"
 #include "mcgmil_device.h"
 #include "mcgmil_error.h"
 
@@ -592,6 +593,40 @@ int mcgmil_stem_forward(const mcgmil_stem_args* a, void* stream) {
     b.workspace = ws + c.bn;
     b.workspace_bytes = c.total - c.bn;
     return mcgmil_detail::bn_finish_bf16(&b, g.part, stats ? c.grid : 0, g.shift, s, hp);
+}
+
+// include/mcgmil_stem_grad_bf16.h: the convolution alone, for training. The kernel instantiation
+// mcgmil_stem_forward launches for running statistics without the pool split, writing straight to y.
+int mcgmil_stem_conv_bf16(const mcgmil_stem_args* a, void* stream) {
+    Geometry G;
+    if (int rc = geometry(a, &G)) return rc;
+    if (a->pool_kernel != 0) return fail(MCGMIL_E_INVALID, "mcgmil_stem_conv_bf16 takes no pooling (pool_kernel must be 0)");
+    if (a->gamma || a->beta || a->running_mean || a->running_var || a->batch_mean || a->batch_invstd)
+        return fail(MCGMIL_E_INVALID, "mcgmil_stem_conv_bf16 applies no BatchNorm: gamma, beta, running_* and batch_* must be NULL");
+    if (!a->x || !a->w || !a->y) return fail(MCGMIL_E_INVALID, "NULL x, w or y");
+    if ((((uintptr_t)a->x) & 3) | (((uintptr_t)a->w | (uintptr_t)a->y) & 15))
+        return fail(MCGMIL_E_ALIGN, "x must be 4-byte and w, y 16-byte aligned");
+    StemGeom g = G.g;
+    g.x = static_cast<const __bf16*>(a->x);
+    g.w = static_cast<const bf16x8*>(a->w);
+    g.y = static_cast<__bf16*>(a->y);
+    g.shift = nullptr;
+    g.part = nullptr;
+    g.gamma = nullptr;
+    const int grid = g.tiles < 2 * cu_count() ? g.tiles : 2 * cu_count();
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (G.KS) {
+        case 1: launch_conv<1>(g, grid, G.lds, false, false, s); break;
+        case 2: launch_conv<2>(g, grid, G.lds, false, false, s); break;
+        case 3: launch_conv<3>(g, grid, G.lds, false, false, s); break;
+        case 4: launch_conv<4>(g, grid, G.lds, false, false, s); break;
+        case 5: launch_conv<5>(g, grid, G.lds, false, false, s); break;
+        case 6: launch_conv<6>(g, grid, G.lds, false, false, s); break;
+        case 7: launch_conv<7>(g, grid, G.lds, false, false, s); break;
+        default: launch_conv<8>(g, grid, G.lds, false, false, s); break;
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MCGMIL_OK : hip_fail(e, "stem_conv_kernel launch");
 }
 
 }  // extern "C"

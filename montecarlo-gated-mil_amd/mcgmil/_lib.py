@@ -78,6 +78,10 @@ BN_GRAD_BF16_EXPORTED = ("mcgmil_bn_grad_bf16_args_size", "mcgmil_bn_grad_worksp
 POOL_GRAD_BF16_EXPORTED = ("mcgmil_batchnorm_pool_train_bf16", "mcgmil_bn_pool_grad_bf16_args_size",
                            "mcgmil_bn_pool_grad_workspace_size_bf16", "mcgmil_batchnorm_pool_backward_bf16")
 
+# include/mcgmil_stem_grad_bf16.h (the bf16 stem convolution alone and its weight gradient; additive as well)
+STEM_GRAD_BF16_EXPORTED = ("mcgmil_stem_conv_bf16", "mcgmil_stem_grad_bf16_args_size",
+                           "mcgmil_stem_wgrad_workspace_size_bf16", "mcgmil_stem_wgrad_bf16")
+
 _vp = ctypes.c_void_p
 
 
@@ -228,6 +232,15 @@ class StemArgs(ctypes.Structure):
         ("batch_mean", _vp), ("batch_invstd", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
         ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class StemGradBf16Args(ctypes.Structure):
+    """Mirror of struct mcgmil_stem_grad_bf16_args (include/mcgmil_stem_grad_bf16.h)."""
+    _fields_ = [
+        ("fwd", StemArgs), ("dy", _vp), ("dw", _vp),
+        ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+        ("chunk_pixels", ctypes.c_int64), ("reserved", ctypes.c_int64),
     ]
 
 
@@ -434,6 +447,17 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     L.mcgmil_pack_stem_weights.restype = ctypes.c_int
     L.mcgmil_stem_forward.argtypes = [ps, _vp]
     L.mcgmil_stem_forward.restype = ctypes.c_int
+    psg = ctypes.POINTER(StemGradBf16Args)
+    L.mcgmil_stem_conv_bf16.argtypes = [ps, _vp]
+    L.mcgmil_stem_conv_bf16.restype = ctypes.c_int
+    L.mcgmil_stem_grad_bf16_args_size.restype = ctypes.c_size_t
+    L.mcgmil_stem_wgrad_workspace_size_bf16.argtypes = [psg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_stem_wgrad_workspace_size_bf16.restype = ctypes.c_int
+    L.mcgmil_stem_wgrad_bf16.argtypes = [psg, _vp]
+    L.mcgmil_stem_wgrad_bf16.restype = ctypes.c_int
+    if L.mcgmil_stem_grad_bf16_args_size() != ctypes.sizeof(StemGradBf16Args):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_stem_grad_bf16_args)={L.mcgmil_stem_grad_bf16_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(StemGradBf16Args)} bytes")
     L.mcgmil_mfma_calib_flops_per_step.argtypes = [ctypes.c_int]
     L.mcgmil_mfma_calib_flops_per_step.restype = ctypes.c_int64
     L.mcgmil_mfma_calib.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, _vp, _vp, _vp]

@@ -65,6 +65,12 @@ torch.ops.mcgmil.bn_pool_bf16: `batchnorm_pool_stats_bf16` is its forward
 (mcgmil_batchnorm_pool_train_bf16: batchnorm_act's pooled bf16 output bit for bit, plus the argmax
 codes taken on the unrounded fp32 value), `batchnorm_pool_backward_bf16` its HIP backward
 (include/mcgmil_pool_grad_bf16.h).
+Inside `native_stem_conv_bf16_training()` (enable_bf16_stem_conv_training()) `run_stem` sends a
+`stem_conv_bf16_trainable` convolution that autograd tracks (the 7x7 stem under bf16 autocast) to
+torch.ops.mcgmil.stem_conv_bf16: `stem_conv_bf16` is its forward (mcgmil_stem_conv_bf16: the
+inference stem's MFMA kernel straight from the NCHW instances, without the BatchNorm),
+`stem_conv_bf16_wgrad` the bf16 HIP weight gradient with fp32 output
+(include/mcgmil_stem_grad_bf16.h).
 
 How the bindings are laid out: every operation is bound once, with the dtype as a parameter, and
 the public fp32 / bf16 names are thin wrappers over it. `_ptr`, `_stream` and `_workspace` do the
@@ -1516,11 +1522,150 @@ def stem(conv: nn.Conv2d, bn: nn.BatchNorm2d, relu: bool, pool: Optional[nn.MaxP
     return y
 
 
+# ---------------------------------------------------------------- bf16 stem convolution backward
+_native_stem_conv_bf16_training = False
+
+
+@contextlib.contextmanager
+def native_stem_conv_bf16_training(flag: bool = True):
+    """Inside this context `run_stem` sends a `stem_conv_bf16_trainable` convolution that autograd
+    tracks and torch would run in bf16 (a bf16 input, or torch.autocast("cuda", torch.bfloat16): the
+    7x7 stem of the NCHW instances) to the differentiable op torch.ops.mcgmil.stem_conv_bf16: the
+    bf16 MFMA forward kernel of the inference stem without its BatchNorm, and the bf16 HIP weight
+    gradient of include/mcgmil_stem_grad_bf16.h. Off outside it: the opt-in of
+    MultiHeadGatedAttentionMIL.enable_bf16_stem_conv_training()."""
+    global _native_stem_conv_bf16_training
+    before, _native_stem_conv_bf16_training = _native_stem_conv_bf16_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_stem_conv_bf16_training = before
+
+
+def stem_conv_bf16_untrainable_reason(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
+    """Why conv on x is not a convolution whose forward AND weight gradient run on the bf16 stem
+    kernels (mcgmil_stem_conv_bf16, mcgmil_stem_wgrad_bf16; include/mcgmil_stem_grad_bf16.h), or
+    None when it is: a CUDA [N, 1..4, H, W] fp32 or bf16 activation (any layout: it is cast to
+    bf16 NCHW) whose bf16 copy stays below 2 GiB, an fp32 (master) or bf16 weight, a bias-free
+    groups=1 dilation-1 zero-padded Conv2d(C, 64, k, stride 2) with a square kernel and padding,
+    k + (pad & 1) <= 8, an even width, OW <= 125 and batch * OH * OW < 2^31 - 256. Says nothing
+    about autograd or autocast."""
+    if not isinstance(conv, nn.Conv2d):
+        return "not an nn.Conv2d"
+    if not (x.is_cuda and x.dim() == 4):
+        return "the activation is not a 4-d CUDA tensor"
+    if x.dtype not in _DT:
+        return "the activation must be fp32 or bf16"
+    if conv.weight.dtype not in _DT:
+        return "the weight must be fp32 or bf16"
+    if conv.groups != 1 or conv.bias is not None or conv.padding_mode != "zeros":
+        return "only a bias-free groups=1 zero-padded convolution"
+    if _square(conv.dilation) != 1 or _square(conv.stride) != 2 or not isinstance(conv.padding, tuple) or \
+            _square(conv.padding) is None or _square(conv.kernel_size) is None:
+        return "dilation 1, stride 2, a square kernel and a square integer padding"
+    k, pad = conv.kernel_size[0], conv.padding[0]
+    if k + (pad & 1) > 8:
+        return "kernel + (pad & 1) must be at most 8"
+    if not 1 <= conv.in_channels <= 4:
+        return "in_channels must be in 1..4"
+    if conv.out_channels != 64:
+        return "out_channels must be 64"
+    N, C, H, W = x.shape
+    if C != conv.in_channels:
+        return "the activation's channels are not the convolution's in_channels"
+    if x.numel() == 0:
+        return "the activation must be non-empty"
+    if W % 2:
+        return "the width must be even"
+    if H + 2 * pad < k or W + 2 * pad < k:
+        return "the kernel does not fit the padded input"
+    oh, ow = _out_hw(H, W, k, k, 2, pad)
+    if ow > 125:
+        return "the output width must be at most 125"
+    if x.numel() * 2 >= 2 ** 31:
+        return "the bf16 activation must be smaller than 2 GiB"
+    if N * oh * ow >= 2 ** 31 - 256:
+        return "batch * OH * OW must be below 2^31 - 256"
+    return None
+
+
+def stem_conv_bf16_trainable(conv: nn.Module, x: torch.Tensor) -> bool:
+    """stem_conv_bf16_untrainable_reason(conv, x) is None. Says nothing about autograd."""
+    return stem_conv_bf16_untrainable_reason(conv, x) is None
+
+
+def _stem_bf16_input(name: str, conv: nn.Module, x: torch.Tensor) -> torch.Tensor:
+    reason = stem_conv_bf16_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"{name}: {reason} (see stem_conv_bf16_trainable)")
+    return x.detach().to(torch.bfloat16).contiguous()      # as features.stem casts it
+
+
+def stem_conv_bf16(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """z = conv(x) (channels-last bf16 [N, 64, OH, OW]) for a `stem_conv_bf16_trainable`
+    convolution: the stem kernel of `stem` without its BatchNorm (mcgmil_stem_conv_bf16; bf16
+    operands, fp32 accumulation, one rounding). x is cast to bf16 NCHW as `stem` casts it; z may
+    exceed 2 GiB. The forward of torch.ops.mcgmil.stem_conv_bf16."""
+    xb = _stem_bf16_input("stem_conv_bf16", conv, x)
+    L = _lib.load()
+    dev = xb.device
+    a = _stem_args(conv, xb)
+    OH, OW = _out_hw(xb.shape[2], xb.shape[3], a.kernel, a.kernel, 2, a.pad)
+    w = packed_stem_weight(conv, xb)
+    z = torch.empty((xb.shape[0], 64, OH, OW), dtype=torch.bfloat16, device=dev, memory_format=_CL)
+    a.x, a.w, a.y = _ptr(xb), _ptr(w), _ptr(z)
+    _lib.check(L.mcgmil_stem_conv_bf16(ctypes.byref(a), _stream(dev)), "mcgmil_stem_conv_bf16")
+    return z
+
+
+def stem_conv_bf16_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
+    """dW [64, in, k, k] fp32 of conv(x) given dY (bf16 [N, 64, OH, OW]) for a
+    `stem_conv_bf16_trainable` convolution, on the bf16 HIP kernel mcgmil_stem_wgrad_bf16: x cast
+    to bf16 NCHW as the forward read it, bf16 operands, fp32 accumulation. chunk_pixels caps the
+    output pixels per launch chunk (0: the library's default); the result does not depend on it,
+    bitwise."""
+    xb = _stem_bf16_input("stem_conv_bf16_wgrad", conv, x)
+    L = _lib.load()
+    dev = xb.device
+    g = _lib.StemGradBf16Args()
+    g.fwd = _stem_args(conv, xb)
+    a = g.fwd
+    shape = (a.batch, 64) + _out_hw(a.height, a.width, a.kernel, a.kernel, 2, a.pad)
+    if tuple(dy.shape) != shape or dy.dtype != torch.bfloat16 or dy.device != dev:
+        raise ValueError(f"dy must be bf16 {shape} on x's device")
+    dy = dy.contiguous(memory_format=_CL)
+    dw = torch.empty((64, a.in_channels, a.kernel, a.kernel), dtype=torch.float32, device=dev)
+    a.x, g.dy, g.dw = _ptr(xb), _ptr(dy), _ptr(dw)
+    g.chunk_pixels = int(chunk_pixels)
+    _workspace(L.mcgmil_stem_wgrad_workspace_size_bf16, "mcgmil_stem_wgrad_workspace_size_bf16", g, dev)
+    _lib.check(L.mcgmil_stem_wgrad_bf16(ctypes.byref(g), _stream(dev)), "mcgmil_stem_wgrad_bf16")
+    return dw
+
+
+def stem_conv_bf16_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """layer(x) through the differentiable op torch.ops.mcgmil.stem_conv_bf16 (mcgmil.library)."""
+    return _conv_op("stem_conv_bf16", layer, x)
+
+
+def _stem_conv_bf16_routed(conv: nn.Module, x: torch.Tensor) -> bool:
+    if not (_native_stem_conv_bf16_training and isinstance(conv, nn.Conv2d) and torch.is_grad_enabled()
+            and (conv.weight.requires_grad or x.requires_grad)):
+        return False
+    bf16 = x.dtype == torch.bfloat16 or \
+        (torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+    return bf16 and stem_conv_bf16_trainable(conv, x)
+
+
 def run_stem(conv: nn.Module, bn: nn.Module, pool: Optional[nn.Module], x: torch.Tensor) -> torch.Tensor:
     """The backbone's stem: the fused kernel when `stem_fusable`, else conv + bn_act (on the GPU
-    with a channels-last activation, so the blocks after it stay on the fused path)."""
+    with a channels-last activation, so the blocks after it stay on the fused path). Inside
+    native_stem_conv_bf16_training() a `stem_conv_bf16_trainable` convolution that autograd tracks
+    and torch would run in bf16 goes to torch.ops.mcgmil.stem_conv_bf16, straight from the NCHW
+    input, and bn_act takes the rest of the stem."""
     if stem_fusable(conv, bn, pool, x):
         return stem(conv, bn, True, pool, x)
+    if _stem_conv_bf16_routed(conv, x):
+        return bn_act(bn, stem_conv_bf16_op(conv, x), True, pool=pool)
     if x.is_cuda and x.dim() == 4:
         x = x.contiguous(memory_format=torch.channels_last)
     if isinstance(conv, nn.Conv2d) and conv32_fusable(conv, x) and isinstance(bn, nn.BatchNorm2d) \

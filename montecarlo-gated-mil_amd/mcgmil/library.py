@@ -33,6 +33,9 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.bn_pool_bf16_backward(z, argmax, dy, weight?, mean, invstd, k, stride, pad, need_dz,
                                            need_dw) -> (dz, dweight, dbias)
 
+    torch.ops.mcgmil.stem_conv_bf16(x, weight, stride, pad) -> y
+    torch.ops.mcgmil.stem_conv_bf16_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -95,6 +98,18 @@ instead; both are subgradients of the same y). Its formula saves the same tensor
 invstd and weight alone, and calls bn_pool_bf16_backward (features.batchnorm_pool_backward_bf16,
 include/mcgmil_pool_grad_bf16.h), which has no formula itself: dz comes back bf16, dweight and
 dbias fp32.
+
+stem_conv_bf16 is the stem convolution in mixed precision (features.stem_conv_bf16_trainable: x
+[N, 1..4, H, W] fp32 or bf16 in ANY layout -- it is cast to bf16 NCHW, the layout the stem kernel
+reads; weight [64, in, k, k], the fp32 master or bf16; stride 2): its forward is the inference
+stem's bf16 MFMA kernel without the BatchNorm (features.stem_conv_bf16), y bf16 channels-last; its
+formula saves x and weight (x as it came in: the cast is made again in the backward instead of
+keeping a bf16 copy alive through the step) and calls stem_conv_bf16_backward, which has no formula
+itself. dw always comes from the bf16 HIP kernel of include/mcgmil_stem_grad_bf16.h
+(features.stem_conv_bf16_wgrad; MCGMIL_CONV_GRAD does not matter) and comes back in the weight's
+dtype, so the fp32 master gets it unrounded; dx, only when asked for (the model never does), from
+aten.convolution_backward on bf16 tensors, bf16 channels-last. The two names are listed in
+STEM_BF16_OPS, not in __all__.
 
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
@@ -232,13 +247,15 @@ def _empty_cl(shape, dtype, like: torch.Tensor, need: bool = True) -> torch.Tens
 
 
 def _conv_family(name: str, dtype: torch.dtype, refusal: Callable, forward: str, backward: Callable,
-                 cast_dy: bool, dw_dtype: Optional[torch.dtype]):
+                 cast_dy: bool, dw_dtype: Optional[torch.dtype], nchw_x: bool = False):
     """Register mcgmil::<name> and mcgmil::<name>_backward, a convolution's op of `dtype`.
     refusal(shim, x): why the op does not take them (the ValueError's text), or None; forward: the
     name of the features function; backward(shim, x, dy, need_dx, need_dw) -> (dx | None, dw | None);
-    cast_dy: dy is cast to `dtype` first; dw_dtype: the fake dw's dtype (None: the weight's)."""
+    cast_dy: dy is cast to `dtype` first; dw_dtype: the fake dw's dtype (None: the weight's);
+    nchw_x: x goes to the features functions in the layout it has (the stem reads NCHW) instead
+    of channels-last."""
     def shim(x, weight, stride, pad):
-        x = _channels_last(x)
+        x = x.detach() if nchw_x else _channels_last(x)
         conv = features._ConvShim(weight, stride, pad)
         why = refusal(conv, x)
         if why is not None:
@@ -316,6 +333,25 @@ stem_conv_f32, stem_conv_f32_backward = _conv_family(
 conv2d_bf16, conv2d_bf16_backward = _conv_family(
     "conv2d_bf16", torch.bfloat16, _named_refusal("conv2d_bf16", "conv_bf16_untrainable_reason", "conv_bf16_trainable"),
     "conv2d_bf16", lambda *a: features.conv2d_bf16_backward(*a), cast_dy=True, dw_dtype=None)
+
+
+def _stem_conv_bf16_grads(conv, x, dy, need_dx, need_dw):
+    dy = dy.contiguous(memory_format=_CL)
+    dw = features.stem_conv_bf16_wgrad(conv, x, dy).to(conv.weight.dtype) if need_dw else None
+    dx = None
+    if need_dx:     # no native data gradient: the model never asks for one (the instances do not require grad)
+        dx = features._aten_conv_backward_bf16(conv, x.to(torch.bfloat16).contiguous(memory_format=_CL), dy, True, False)[0]
+    return dx, dw
+
+
+# The bf16 stem convolution's ops. They are not in __all__: tests/fixtures/features_bindings.json
+# records __all__ as the op list of the merged fp32 / bf16 twins, and this op has no fp32 twin of
+# the same shape (stem_conv_f32 reads channels-last fp32, this one NCHW).
+STEM_BF16_OPS = ("stem_conv_bf16", "stem_conv_bf16_backward")
+stem_conv_bf16, stem_conv_bf16_backward = _conv_family(
+    "stem_conv_bf16", torch.bfloat16,
+    _named_refusal("stem_conv_bf16", "stem_conv_bf16_untrainable_reason", "stem_conv_bf16_trainable"),
+    "stem_conv_bf16", _stem_conv_bf16_grads, cast_dy=True, dw_dtype=None, nchw_x=True)
 
 
 def _bn_act_family(name: str, dtype: torch.dtype, forward: str, backward: str, mixed: bool):

@@ -109,6 +109,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._bf16_backbone_training = False
         self._bf16_norm_training = False
         self._bf16_stem_training = False
+        self._bf16_stem_conv_training = False
 
     # ------------------------------------------------------------------ parameters
     def _gate_linears(self):
@@ -290,14 +291,17 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         the forward kernel again as the stride-1 data gradient; default: aten.convolution_backward
         on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
         by layer, so the stem convolution, BatchNorm, ReLU and the pools are the torch layers under
-        autocast, unless enable_bf16_norm_training() (the blocks' BatchNorms) or
-        enable_bf16_stem_training() (the stem's bn1 / relu / maxpool) is on as well. The head stays
+        autocast, unless enable_bf16_norm_training() (the blocks' BatchNorms),
+        enable_bf16_stem_training() (the stem's bn1 / relu / maxpool) or
+        enable_bf16_stem_conv_training() (the stem convolution) is on as well. The head stays
         fp32. Eval mode, no_grad and the default are unchanged. Off by default; switching it off
-        switches enable_bf16_norm_training and enable_bf16_stem_training off too; returns self."""
+        switches enable_bf16_norm_training, enable_bf16_stem_training and
+        enable_bf16_stem_conv_training off too; returns self."""
         self._bf16_backbone_training = bool(flag)
         if not flag:
             self._bf16_norm_training = False
             self._bf16_stem_training = False
+            self._bf16_stem_conv_training = False
         return self
 
     def enable_bf16_norm_training(self, flag=True):
@@ -309,7 +313,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         fused bf16 HIP forward and the HIP backward of include/mcgmil_bn_grad_bf16.h instead of
         torch's batch_norm / add / relu kernels and their backward (timings in DESIGN.md §4). It
         does not depend on MCGMIL_CONV_GRAD. The stem's bn1 / relu / maxpool (unless
-        enable_bf16_stem_training() is on), the stem convolution and the head stay as they are. A
+        enable_bf16_stem_training() is on), the stem convolution (unless
+        enable_bf16_stem_conv_training() is on) and the head stay as they are. A
         method of its own, so that enable_bf16_backbone_training keeps its signature. Off by
         default; enable_bf16_backbone_training(False) switches it off; returns self."""
         self._bf16_norm_training = bool(flag)
@@ -327,9 +332,27 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         taps of a window round to the same bf16 value the gradient goes to the one whose unrounded
         value is larger, not to the first as under torch (include/mcgmil_pool_grad_bf16.h). It
         depends on neither enable_bf16_norm_training() nor MCGMIL_CONV_GRAD. The stem convolution
-        stays the torch layer under autocast. A method of its own, so that the existing signatures
+        stays the torch layer under autocast (unless enable_bf16_stem_conv_training() is on). A method
+        of its own, so that the existing signatures
         stay. Off by default; enable_bf16_backbone_training(False) switches it off; returns self."""
         self._bf16_stem_training = bool(flag)
+        return self
+
+    def enable_bf16_stem_conv_training(self, flag=True):
+        """On top of enable_bf16_backbone_training(), and in effect only while that is on: forward()
+        in train mode additionally sends the stem convolution conv1, when
+        features.stem_conv_bf16_trainable (the NCHW instances with 1..4 channels, a bias-free
+        stride-2 Conv2d(C, 64, k) with k + (pad & 1) <= 8, an even width, OW <= 125), through the
+        differentiable op torch.ops.mcgmil.stem_conv_bf16: the inference stem's bf16 MFMA kernel
+        straight from the NCHW instances (no channels-last copy of x, no batch chunks, no
+        torch.cat of the output) and the bf16 HIP weight gradient of
+        include/mcgmil_stem_grad_bf16.h, written in fp32 into the fp32 master weight's .grad and
+        bitwise repeatable, instead of the torch layer under autocast and
+        aten.convolution_backward (timings in DESIGN.md §4). It depends on neither
+        enable_bf16_norm_training() nor enable_bf16_stem_training() nor MCGMIL_CONV_GRAD. A method
+        of its own, so that the existing signatures stay. Off by default;
+        enable_bf16_backbone_training(False) switches it off; returns self."""
+        self._bf16_stem_conv_training = bool(flag)
         return self
 
     def _live_head(self):
@@ -387,7 +410,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                 if self._bf16_backbone_training:
                     with torch.autocast("cuda", torch.bfloat16), features.native_conv_bf16_training(), \
                             features.native_norm_bf16_training(self._bf16_norm_training), \
-                            features.native_stem_bf16_training(self._bf16_stem_training):
+                            features.native_stem_bf16_training(self._bf16_stem_training), \
+                            features.native_stem_conv_bf16_training(self._bf16_stem_conv_training):
                         H = self.extract_features(x)
                 else:
                     H = self.extract_features(x)
