@@ -82,6 +82,10 @@ POOL_GRAD_BF16_EXPORTED = ("mcgmil_batchnorm_pool_train_bf16", "mcgmil_bn_pool_g
 STEM_GRAD_BF16_EXPORTED = ("mcgmil_stem_conv_bf16", "mcgmil_stem_grad_bf16_args_size",
                            "mcgmil_stem_wgrad_workspace_size_bf16", "mcgmil_stem_wgrad_bf16")
 
+# include/mcgmil_conv_dgrad_bf16.h (the bf16 convolution's direct data gradient; additive as well)
+CONV_DGRAD_BF16_EXPORTED = ("mcgmil_conv_dgrad_bf16_args_size", "mcgmil_conv_dgrad_classes_bf16",
+                            "mcgmil_conv2d_dgrad_bf16")
+
 _vp = ctypes.c_void_p
 
 
@@ -176,6 +180,12 @@ class ConvGradBf16Args(ctypes.Structure):
 class ConvDgradArgs(ctypes.Structure):
     """Mirror of struct mcgmil_conv_dgrad_args (include/mcgmil_conv_dgrad.h)."""
     _fields_ = [("fwd", ConvArgs), ("dy", _vp), ("w_t", _vp), ("dx", _vp), ("reserved", ctypes.c_int64)]
+
+
+class ConvDgradBf16Args(ctypes.Structure):
+    """Mirror of struct mcgmil_conv_dgrad_bf16_args (include/mcgmil_conv_dgrad_bf16.h): the fields of
+    mcgmil_conv_dgrad_args, with bf16 dy / dx and w_t as [kh][kw][in][out] bf16."""
+    _fields_ = list(ConvDgradArgs._fields_)
 
 
 class BnGradArgs(ctypes.Structure):
@@ -397,6 +407,16 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     if L.mcgmil_conv_dgrad_args_size() != ctypes.sizeof(ConvDgradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_dgrad_args)={L.mcgmil_conv_dgrad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvDgradArgs)} bytes")
+    pdb = ctypes.POINTER(ConvDgradBf16Args)
+    L.mcgmil_conv_dgrad_bf16_args_size.restype = ctypes.c_size_t
+    L.mcgmil_conv_dgrad_classes_bf16.argtypes = [pdb, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64),
+                                                 ctypes.POINTER(ctypes.c_int64)]
+    L.mcgmil_conv_dgrad_classes_bf16.restype = ctypes.c_int
+    L.mcgmil_conv2d_dgrad_bf16.argtypes = [pdb, _vp]
+    L.mcgmil_conv2d_dgrad_bf16.restype = ctypes.c_int
+    if L.mcgmil_conv_dgrad_bf16_args_size() != ctypes.sizeof(ConvDgradBf16Args):
+        raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_dgrad_bf16_args)={L.mcgmil_conv_dgrad_bf16_args_size()} "
+                          f"but the ctypes mirror is {ctypes.sizeof(ConvDgradBf16Args)} bytes")
     pbg = ctypes.POINTER(BnGradArgs)
     L.mcgmil_bn_grad_args_size.restype = ctypes.c_size_t
     L.mcgmil_bn_grad_workspace_size.argtypes = [pbg, ctypes.POINTER(ctypes.c_size_t)]

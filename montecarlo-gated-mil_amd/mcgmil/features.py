@@ -53,8 +53,10 @@ tracks (a bf16 activation, as the blocks see it under torch.autocast) to
 torch.ops.mcgmil.conv2d_bf16: `conv2d_bf16` is the forward (the bf16 MFMA kernel of `conv2d`),
 `conv2d_bf16_wgrad` the bf16 HIP weight gradient with fp32 output
 (include/mcgmil_conv_grad_bf16.h), `conv2d_bf16_dgrad` the data gradient (the forward kernel on the
-flipped weight for stride 1, else aten), `conv2d_bf16_backward` the op's backward on the route
-MCGMIL_CONV_GRAD names (native or direct: the HIP kernels; default aten.convolution_backward).
+flipped weight for stride 1, else aten), `conv2d_bf16_dgrad_direct` the direct bf16 data-gradient
+kernel for stride 1 and 2 (include/mcgmil_conv_dgrad_bf16.h), `conv2d_bf16_backward` the op's
+backward on the route MCGMIL_CONV_GRAD names (native: the HIP kernels, aten for the stride-2 data
+gradient; direct: the direct kernel in aten's place; default aten.convolution_backward).
 Inside `native_norm_bf16_training()` (enable_bf16_norm_training()) `bn_act` sends a
 pool-free `bn_bf16_trainable` BatchNorm (+ residual add) (+ ReLU) that autograd tracks to
 torch.ops.mcgmil.bn_act_bf16: `batchnorm_act_stats_bf16` is its forward (mcgmil_batchnorm_act in
@@ -256,6 +258,8 @@ _CONV_BF16_TRAINABLE = dict(fp32=False, weights=(torch.float32, torch.bfloat16),
                             below_2gib=True, max_hw=16383)
 _DGRAD_DIRECT = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="16", of_dy=True,
                      channels_last=False, pixels=None)
+_DGRAD_BF16_DIRECT = dict(fp32=False, weights=(torch.float32, torch.bfloat16), autocast="ignore", in_channels="64",
+                          of_dy=True, channels_last=False, pixels=None, below_2gib=True)
 
 
 def conv_fusable(conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -750,8 +754,9 @@ def conv2d_bf16_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_
 def dgrad_bf16_native(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
     """Whether conv2d_bf16_dgrad runs this convolution's data gradient on the bf16 forward kernel:
     stride 1, a square kernel (one pad k - 1 - p for both axes) and a dY below 2 GiB (the forward
-    kernel's input limit). Otherwise aten.convolution_backward: there is no bf16 direct or strided
-    data-gradient kernel."""
+    kernel's input limit). Otherwise conv2d_bf16_dgrad takes aten.convolution_backward; the bf16
+    direct kernel for stride 2 and non-square kernels is conv2d_bf16_dgrad_direct, which
+    conv2d_bf16_backward calls on the "direct" route."""
     return _square(conv.stride) == 1 and conv.kernel_size[0] == conv.kernel_size[1] and dy.numel() * 2 < 2 ** 31
 
 
@@ -779,6 +784,41 @@ def conv2d_bf16_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x: torch.Tensor) -> tor
     return dx
 
 
+def dgrad_bf16_direct_supported(conv: nn.Conv2d, dy: torch.Tensor) -> bool:
+    """Whether conv2d_bf16_dgrad_direct implements this convolution's data gradient for dy: a CUDA
+    bf16 dy [batch, out_channels, OH, OW] below 2 GiB, an fp32 (master) or bf16 weight, and a
+    bias-free groups=1 dilation-1 zero-padded convolution with kernel 1..7 per axis, stride 1 or 2,
+    pad < kernel and in_channels and out_channels multiples of 64
+    (include/mcgmil_conv_dgrad_bf16.h). A `conv_bf16_trainable` convolution is one unless its dY
+    reaches 2 GiB, which the forward allows while x stays below it."""
+    return _conv_refusal(conv, dy, **_DGRAD_BF16_DIRECT) is None
+
+
+def conv2d_bf16_dgrad_direct(conv: nn.Conv2d, dy: torch.Tensor, x_shape) -> torch.Tensor:
+    """dX (channels-last bf16, shape x_shape) of conv(x) given dY on the direct bf16 HIP
+    data-gradient kernel mcgmil_conv2d_dgrad_bf16, stride 1 and 2, square kernel or not: the
+    residue classes of the input pixels, each a stride-1 implicit GEMM over its own taps on the
+    bf16 MFMA with fp32 accumulation and one rounding (include/mcgmil_conv_dgrad_bf16.h). The
+    weight goes in as one weight.to(bfloat16).permute(2, 3, 1, 0).contiguous(); every element of dX
+    is written exactly once, so two calls agree bitwise. Raises for anything
+    dgrad_bf16_direct_supported refuses."""
+    reason = _conv_refusal(conv, dy, **_DGRAD_BF16_DIRECT)
+    if reason is not None:
+        raise ValueError(f"conv2d_bf16_dgrad_direct: {reason} (dY; see dgrad_bf16_direct_supported)")
+    L = _lib.load()
+    g = _lib.ConvDgradBf16Args()
+    g.fwd = _conv_args(conv, x_shape)
+    if int(x_shape[1]) != conv.in_channels or tuple(dy.shape) != _conv_out_shape(g.fwd):
+        raise ValueError(f"x_shape {tuple(x_shape)} does not belong to this convolution and dy {tuple(dy.shape)}")
+    dy = dy.contiguous(memory_format=_CL)
+    wt = conv.weight.detach().to(torch.bfloat16).permute(2, 3, 1, 0).contiguous()     # [kh][kw][in][out]
+    dev = dy.device
+    dx = torch.empty(tuple(x_shape), dtype=torch.bfloat16, device=dev, memory_format=_CL)
+    g.dy, g.w_t, g.dx = _ptr(dy), _ptr(wt), _ptr(dx)
+    _lib.check(L.mcgmil_conv2d_dgrad_bf16(ctypes.byref(g), _stream(dev)), "mcgmil_conv2d_dgrad_bf16")
+    return dx
+
+
 def conv2d_bf16_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool = True,
                          need_dw: bool = True):
     """(dX bf16 or None, dW in the weight's dtype or None) of conv(x) given dY for a
@@ -786,16 +826,24 @@ def conv2d_bf16_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, nee
     MCGMIL_CONV_GRAD names (conv_grad_route, read on every call). "aten" (the default):
     aten.convolution_backward on bf16 tensors for both gradients. "native": the bf16 HIP weight
     gradient (conv2d_bf16_wgrad; fp32, so an fp32 master weight gets it unrounded) and
-    conv2d_bf16_dgrad. "direct" means "native" for this op: there is no bf16 direct data-gradient
-    kernel."""
+    conv2d_bf16_dgrad (stride 1 and a square kernel: the forward kernel on the flipped weight;
+    else aten, dx only). "direct": as "native" where dgrad_bf16_native holds, and everywhere else
+    (stride 2, a non-square kernel) the direct bf16 HIP data gradient conv2d_bf16_dgrad_direct
+    (include/mcgmil_conv_dgrad_bf16.h) -- no gradient of the convolution leaves the project's
+    kernels, and both repeat bitwise. A dY of 2 GiB or more (the forward takes it while x is below
+    2 GiB) is outside both data-gradient kernels: "native" sends it to aten, "direct" raises."""
     reason = conv_bf16_untrainable_reason(conv, x)
     if reason is not None:
         raise ValueError(f"conv2d_bf16_backward: {reason} (see conv_bf16_trainable)")
     dy = dy.contiguous(memory_format=torch.channels_last)
-    if not conv_grad_native():
+    route = conv_grad_route()
+    if route == "aten":
         return _aten_conv_backward_bf16(conv, x, dy, need_dx, need_dw)
     dw = conv2d_bf16_wgrad(conv, x, dy).to(conv.weight.dtype) if need_dw else None
-    dx = conv2d_bf16_dgrad(conv, dy, x) if need_dx else None
+    dx = None
+    if need_dx:
+        dx = conv2d_bf16_dgrad_direct(conv, dy, x.shape) if route == "direct" and not dgrad_bf16_native(conv, dy) \
+            else conv2d_bf16_dgrad(conv, dy, x)
     return dx, dw
 
 

@@ -79,9 +79,10 @@ channels multiples of 64): its forward is the bf16 MFMA kernel of features.conv2
 formula calls conv2d_bf16_backward (features.conv2d_bf16_backward), which has none itself. With
 MCGMIL_CONV_GRAD=native the weight gradient is the bf16 HIP kernel of
 include/mcgmil_conv_grad_bf16.h (bf16 operands, fp32 accumulation, fp32 dW) and the stride-1 data
-gradient the forward kernel on the flipped weight (stride 2: aten, dx only); =direct means native
-here (there is no bf16 direct data-gradient kernel); else aten.convolution_backward on bf16
-tensors. dw comes back in the weight's dtype and contiguous, dx bf16 channels-last.
+gradient the forward kernel on the flipped weight (stride 2: aten, dx only); =direct is native
+with the direct bf16 HIP data gradient of include/mcgmil_conv_dgrad_bf16.h wherever native takes
+aten (stride 2, a non-square kernel), so no gradient leaves the project's kernels; else
+aten.convolution_backward on bf16 tensors. dw comes back in the weight's dtype and contiguous, dx bf16 channels-last.
 
 bn_act_bf16 is bn_act_f32 in mixed precision: x, residual and y bf16, weight and bias the fp32
 master parameters, mean and invstd fp32 (features.batchnorm_act_stats_bf16: mcgmil_batchnorm_act

@@ -288,8 +288,10 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         bf16 MFMA forward kernel of the inference path, and for the backward the route
         MCGMIL_CONV_GRAD names (native or direct: the bf16 HIP weight gradient of
         include/mcgmil_conv_grad_bf16.h, written in fp32 into the fp32 master weight's .grad, and
-        the forward kernel again as the stride-1 data gradient; default: aten.convolution_backward
-        on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
+        the forward kernel again as the stride-1 data gradient; the stride-2 data gradient is
+        aten's on native and the direct bf16 HIP kernel of include/mcgmil_conv_dgrad_bf16.h on
+        direct, so that on direct no gradient of a routed convolution leaves the project's kernels
+        and the step repeats bitwise; default: aten.convolution_backward on bf16 tensors). The fp32 opt-ins of enable_backbone_training decline under autocast layer
         by layer, so the stem convolution, BatchNorm, ReLU and the pools are the torch layers under
         autocast, unless enable_bf16_norm_training() (the blocks' BatchNorms),
         enable_bf16_stem_training() (the stem's bn1 / relu / maxpool) or
