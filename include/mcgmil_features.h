@@ -215,6 +215,33 @@ int mcgmil_conv_packed_size_f32(const mcgmil_conv_args* a, size_t* floats);
 int mcgmil_conv_stats_parts_f32(const mcgmil_conv_args* a, int32_t* parts);
 int mcgmil_pack_conv_weights_f32(const mcgmil_conv_args* a, const void* weight, void* packed, void* stream);
 int mcgmil_conv2d_f32(const mcgmil_conv_args* a, void* stream);
+/* mcgmil_conv2d_f32 on split-bf16 matrix instructions ("bf16x3", the bfloat16_3x mode of
+ * torch.set_float32_matmul_precision("high") for the backbone's fp32 torch.nn.Conv2d.forward):
+ * x, y, stats, in_ab and in_relu exactly as mcgmil_conv2d_f32's -- fp32 NHWC in and out, nothing
+ * rounded for storage -- at 3/16 of its matrix-pipe cost. Opt-in; not bitwise mcgmil_conv2d_f32.
+ *   Domain: mcgmil_conv2d_f32's with in_channels a multiple of 32 (every block convolution of
+ *     ResNet-18/34/50); anything else, the gather mode (the 3-channel stem) and in_channels 16 or
+ *     48 included, is MCGMIL_E_UNSUPPORTED. x, w, y and in_ab 16-byte aligned, stats 4-byte.
+ *   Split (the numerics contract): every operand v becomes hi = bf16_rne(v) and
+ *     lo = bf16_rne(v - float(hi)); the subtraction is exact in fp32, and |v - hi - lo| <= 2^-16 |v|.
+ *     Activations are split as the kernel stages them, after max(fmaf(x, a_c, b_c), floor) when
+ *     in_ab is given, so conv(relu(bn(x))) stays bitwise equal to mcgmil_batchnorm_act followed by
+ *     this call. Weights are split once by mcgmil_pack_conv_weights_f32x3 into the kernel's own
+ *     layout [K step of 32 input channels of a tap][hi, lo][out_channels][32] bf16
+ *     (mcgmil_conv_packed_size_f32x3 counts it in 4-byte units: one per weight).
+ *   Accumulation: per 32 input channels of a tap three v_mfma_f32_16x16x32_bf16 products,
+ *     hi_w hi_x + hi_w lo_x + lo_w hi_x, into one fp32 accumulator; the lo_w lo_x term (<= 2^-16 of
+ *     |w x|) is dropped. Products of bf16 terms are exact in fp32. No split-K, no atomics, one
+ *     writer per element: two launches give the same bits. Worst case against the exact sum:
+ *     3 * 2^-16 * conv(|x|, |w|) plus the fp32 accumulation error.
+ *   Edge values: finite inputs (after in_ab) below 2^127 in magnitude are the contract. Inf and NaN
+ *     inputs, and values whose lo term is a bf16 denormal, are not guaranteed to give what
+ *     mcgmil_conv2d_f32 gives.
+ *   stats: one block per output-pixel tile, parts = mcgmil_conv_stats_parts_f32x3(). */
+int mcgmil_conv_packed_size_f32x3(const mcgmil_conv_args* a, size_t* floats);
+int mcgmil_conv_stats_parts_f32x3(const mcgmil_conv_args* a, int32_t* parts);
+int mcgmil_pack_conv_weights_f32x3(const mcgmil_conv_args* a, const void* weight, void* packed, void* stream);
+int mcgmil_conv2d_f32x3(const mcgmil_conv_args* a, void* stream);
 int mcgmil_bn_workspace_size(const mcgmil_bn_args* a, size_t* bytes);
 int mcgmil_batchnorm_act(const mcgmil_bn_args* a, void* stream);
 /* The per-channel coefficients mcgmil_batchnorm_act would apply, without the apply pass:

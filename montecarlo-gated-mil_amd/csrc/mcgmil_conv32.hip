@@ -20,14 +20,15 @@
 // elements as they are written to LDS (after the step's MFMAs, so the loads stay in flight), so
 // relu(bn(x)) is never materialised. STATS: the epilogue also reduces its outputs to one
 // (count, mean, M2) block per channel of the tile (shifted sums over a wave's pixels, then the
-// waves sharing the channels; tile_stats) for the BatchNorm that follows, so the activation is
-// not re-read for statistics.
+// waves sharing the channels; tile_stats in mcgmil_conv_tile_stats.h) for the BatchNorm that
+// follows, so the activation is not re-read for statistics.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "../../include/mcgmil.h"
 #include "../../include/mcgmil_features.h"
+#include "mcgmil_conv_tile_stats.h"
 #include "mcgmil_device.h"
 #include "mcgmil_error.h"
 
@@ -36,7 +37,8 @@ namespace {
 using mcgmil_detail::fail;
 using mcgmil_detail::hip_fail;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+using mcgmil::f32x4;
+using mcgmil::tile_stats;
 
 struct Conv32Geom {
     int N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW;
@@ -64,72 +66,6 @@ struct Tile {
     static constexpr int STAGE = kK * (AS + BS);                             // floats per stage
     static constexpr int A4 = kK * BN_CO / 4 / 256, B4 = kK * BM_PX / 4 / 256;   // float4 per thread
 };
-
-// Lane 15 of every row of 16 lanes gets the row's sum (DPP row_shr 1, 2, 4, 8: four VALU adds,
-// no LDS traffic); the other lanes hold partial sums.
-__device__ __forceinline__ float row_sum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xF, 0xF, true));
-    return v;
-}
-
-// The tile's statistics (STATS): see the header comment. acc[i][j]: channels 16 i + 4 kl + v of
-// the wave's 64, pixels 16 j + cl; the wave's first nval pixels are valid. Per channel the 16
-// lanes sum x - sh and (x - sh)^2 around sh = the channel's output at the wave's first pixel
-// (lane 16 kl, j = 0), row_sum16 adds the lanes, and lane 16 kl + 15 turns the sums into the
-// wave's (count, mean, M2); the waves sharing the channels are merged by chan_merge. One channel quad i
-// at a time, so few registers are live beside the accumulators, and no division per lane.
-template <int WCO, int WPX>
-__device__ __forceinline__ void tile_stats(const f32x4 (&acc)[4][4], int nval, int wco, int wpx, int lane,
-                                           float* red, float* stats, long long row, int Cout, int co0) {
-    using T = Tile<WCO, WPX>;
-    const int kl = lane >> 4, cl = lane & 15;
-    const float n = (float)nval, rn = nval > 0 ? 1.f / n : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float sh[4], S[4], Q[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            sh[v] = __shfl(acc[i][0][v], kl * 16, 64);
-            float sum = 0.f, sq = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float d = 16 * j + cl < nval ? acc[i][j][v] - sh[v] : 0.f;
-                sum += d;
-                sq = fmaf(d, d, sq);
-            }
-            S[v] = sum;
-            Q[v] = sq;
-        }
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            S[v] = row_sum16(S[v]);
-            Q[v] = row_sum16(Q[v]);
-        }
-        if (cl == 15) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int local = wco * 64 + 16 * i + 4 * kl + v;
-                red[(wpx * 3 + 0) * T::BN_CO + local] = n;
-                red[(wpx * 3 + 1) * T::BN_CO + local] = nval > 0 ? fmaf(S[v], rn, sh[v]) : 0.f;
-                red[(wpx * 3 + 2) * T::BN_CO + local] = nval > 0 ? fmaxf(Q[v] - S[v] * S[v] * rn, 0.f) : 0.f;
-            }
-        }
-    }
-    __syncthreads();
-    for (int local = threadIdx.x; local < T::BN_CO; local += 256) {
-        float cn = red[local], cm[1] = {red[T::BN_CO + local]}, cM2[1] = {red[2 * T::BN_CO + local]};
-        for (int w = 1; w < WPX; ++w) {
-            const float mb[1] = {red[(w * 3 + 1) * T::BN_CO + local]}, M2b[1] = {red[(w * 3 + 2) * T::BN_CO + local]};
-            mcgmil::chan_merge<1>(cn, cm, cM2, red[(w * 3) * T::BN_CO + local], mb, M2b);
-        }
-        stats[((size_t)row * 3 + 0) * Cout + co0 + local] = cn;
-        stats[((size_t)row * 3 + 1) * Cout + co0 + local] = cm[0];
-        stats[((size_t)row * 3 + 2) * Cout + co0 + local] = cM2[0];
-    }
-}
 
 // STATS: 4 waves per SIMD (<= 128 registers with the 64 accumulators): the 128 x 128 tile's LDS
 // allows 4 workgroups per CU, and without the bound the statistics epilogue's peak (148 registers)
@@ -306,7 +242,7 @@ __global__ __launch_bounds__(256, STATS ? 4 : 1) void conv32_kernel(const Conv32
     }
     if constexpr (STATS) {   // the stages are free: the K loop ended with a barrier
         const long long left = g.P - (px0 + wpx * 64);
-        tile_stats<WCO, WPX>(acc, left < 0 ? 0 : (left > 64 ? 64 : (int)left), wco, wpx, lane, smem32,
+        tile_stats<T::BN_CO, WPX>(acc, left < 0 ? 0 : (left > 64 ? 64 : (int)left), wco, wpx, lane, smem32,
                              g.stats, blockIdx.x, g.Cout, co0);
     }
 }

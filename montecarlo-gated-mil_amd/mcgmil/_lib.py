@@ -43,6 +43,8 @@ EXPORTED = (
     "mcgmil_conv_workspace_size",
     "mcgmil_conv_packed_size_f32", "mcgmil_pack_conv_weights_f32", "mcgmil_conv2d_f32",
     "mcgmil_conv_stats_parts_f32",
+    "mcgmil_conv_packed_size_f32x3", "mcgmil_pack_conv_weights_f32x3", "mcgmil_conv2d_f32x3",
+    "mcgmil_conv_stats_parts_f32x3",
     "mcgmil_stem_args_size", "mcgmil_stem_packed_size", "mcgmil_pack_stem_weights",
     "mcgmil_stem_workspace_size", "mcgmil_stem_forward",
     # include/mcgmil_calib.h (measurement)
@@ -375,6 +377,14 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     L.mcgmil_pack_conv_weights_f32.restype = ctypes.c_int
     L.mcgmil_conv2d_f32.argtypes = [pc, _vp]
     L.mcgmil_conv2d_f32.restype = ctypes.c_int
+    L.mcgmil_conv_packed_size_f32x3.argtypes = [pc, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_conv_packed_size_f32x3.restype = ctypes.c_int
+    L.mcgmil_conv_stats_parts_f32x3.argtypes = [pc, ctypes.POINTER(ctypes.c_int32)]
+    L.mcgmil_conv_stats_parts_f32x3.restype = ctypes.c_int
+    L.mcgmil_pack_conv_weights_f32x3.argtypes = [pc, _vp, _vp, _vp]
+    L.mcgmil_pack_conv_weights_f32x3.restype = ctypes.c_int
+    L.mcgmil_conv2d_f32x3.argtypes = [pc, _vp]
+    L.mcgmil_conv2d_f32x3.restype = ctypes.c_int
     pcg = ctypes.POINTER(ConvGradArgs)
     L.mcgmil_conv_grad_args_size.restype = ctypes.c_size_t
     L.mcgmil_conv_wgrad_workspace_size_f32.argtypes = [pcg, ctypes.POINTER(ctypes.c_size_t)]

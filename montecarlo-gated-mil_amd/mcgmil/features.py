@@ -74,6 +74,11 @@ inference stem's MFMA kernel straight from the NCHW instances, without the Batch
 `stem_conv_bf16_wgrad` the bf16 HIP weight gradient with fp32 output
 (include/mcgmil_stem_grad_bf16.h).
 
+Precision of the fp32 convolutions: `conv2d_f32(..., precision=)` / `float32_conv_precision()` /
+MCGMIL_CONV32_PRECISION send a `conv32x3_fusable` convolution (in_channels a multiple of 32: every
+block convolution) to mcgmil_conv2d_f32x3, the split-bf16 kernel with fp32 storage (three bf16 MFMA
+products per K, "bf16x3"); the stem, other layers and every differentiable op stay exact fp32.
+
 How the bindings are laid out: every operation is bound once, with the dtype as a parameter, and
 the public fp32 / bf16 names are thin wrappers over it. `_ptr`, `_stream` and `_workspace` do the
 marshalling; `_conv_args` fills mcgmil_conv_args (also as the `fwd` of the gradient structs) and
@@ -180,7 +185,7 @@ def _conv_refusal(conv: nn.Module, t: torch.Tensor, *, fp32: bool, weights: Opti
                   in_channels: str, strides: Optional[tuple] = (1, 2), pad_below_kernel: bool = True,
                   out_max: Optional[int] = None, of_dy: bool = False, nonempty: bool = True,
                   channels_last: bool = True, pixels: Optional[str] = "positive", below_2gib: bool = False,
-                  max_hw: Optional[int] = None, autograd: bool = False) -> Optional[str]:
+                  max_hw: Optional[int] = None, autograd: bool = False, device_last: bool = False) -> Optional[str]:
     """Why `conv` on the activation `t` is outside a native convolution's domain: the first clause
     that fails, or None. Every predicate below is this walk with its own keywords:
       fp32          an fp32 activation behind MCGMIL_NATIVE_CONV32, else a bf16 one behind MCGMIL_NATIVE_CONV
@@ -192,13 +197,14 @@ def _conv_refusal(conv: nn.Module, t: torch.Tensor, *, fp32: bool, weights: Opti
       of_dy         t is dY, [batch, out_channels, OH, OW], not x
       pixels        "positive": 1 <= OH, OW and batch * OH * OW < 2^31 - 256; "any": the product alone; None
       below_2gib, max_hw   the bf16 kernels' limits on t: numel * 2 < 2^31, height and width <= max_hw
-      autograd      refuse what autograd tracks (the inference predicates)"""
+      autograd      refuse what autograd tracks (the inference predicates)
+      device_last   ask for a CUDA activation after every other clause, not with the rank"""
     if not (conv32_enabled() if fp32 else conv_enabled()):
         return "the native fp32 convolutions are switched off (MCGMIL_NATIVE_CONV32 / MCGMIL_NATIVE_CONV)" if fp32 \
             else "the native convolutions are switched off (MCGMIL_NATIVE_CONV)"
     if not isinstance(conv, nn.Conv2d):
         return "not an nn.Conv2d"
-    if not (t.is_cuda and t.dim() == 4):
+    if not ((t.is_cuda or device_last) and t.dim() == 4):
         return "the activation is not a 4-d CUDA tensor"
     if fp32:
         if t.dtype != torch.float32 or (weights is not None and conv.weight.dtype not in weights):
@@ -245,6 +251,8 @@ def _conv_refusal(conv: nn.Module, t: torch.Tensor, *, fp32: bool, weights: Opti
         return "the activation must be smaller than 2 GiB, height and width at most 16383"
     if autograd and torch.is_grad_enabled() and (t.requires_grad or conv.weight.requires_grad):
         return "autograd tracks the activation or the weight"
+    if not t.is_cuda:
+        return "the activation is not a CUDA tensor"
     return None
 
 
@@ -252,6 +260,7 @@ _CONV_FUSABLE = dict(fp32=False, weights=(torch.bfloat16,), autocast="bf16", in_
                      pad_below_kernel=False, nonempty=False, pixels=None, below_2gib=True, autograd=True)
 _CONV32_FUSABLE = dict(fp32=True, weights=None, autocast="refuse", in_channels="16 or gather", strides=None,
                        pad_below_kernel=False, nonempty=False, pixels="any", autograd=True)
+_CONV32X3_FUSABLE = dict(_CONV32_FUSABLE, in_channels="32", device_last=True)
 _CONV32_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="16")
 _STEM_CONV_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="1..4", out_max=4096)
 _CONV_BF16_TRAINABLE = dict(fp32=False, weights=(torch.float32, torch.bfloat16), autocast="ignore", in_channels="64",
@@ -404,30 +413,110 @@ def conv32_input_bn(conv: nn.Conv2d, x: torch.Tensor) -> bool:
         conv.in_channels <= 2048
 
 
+# ---------------------------------------------------------------- fp32 convolutions on split bf16 (bf16x3)
+_PRECISIONS = ("fp32", "bf16x3")
+_conv32_precision: Optional[str] = None      # float32_conv_precision's setting (None: the environment's)
+
+
+def conv32_precision() -> str:
+    """The ambient precision of the fp32 convolutions: what float32_conv_precision set, else
+    MCGMIL_CONV32_PRECISION (read on every call): "bf16x3", or "fp32" for anything else."""
+    if _conv32_precision is not None:
+        return _conv32_precision
+    return "bf16x3" if os.environ.get("MCGMIL_CONV32_PRECISION", "fp32") == "bf16x3" else "fp32"
+
+
+def _check_precision(precision: str) -> str:
+    if precision not in _PRECISIONS:
+        raise ValueError(f"precision must be one of {_PRECISIONS}, not {precision!r}")
+    return precision
+
+
+@contextlib.contextmanager
+def float32_conv_precision(precision: str):
+    """Inside this context conv2d_f32 (and with it run_conv, conv_bn_act and the stem fallback)
+    runs every `conv32x3_fusable` convolution at `precision`: "fp32" (mcgmil_conv2d_f32, exact fp32
+    MFMA) or "bf16x3" (mcgmil_conv2d_f32x3: fp32 storage, three bf16 MFMA products per K, about
+    15x fp32's distance from the exact sum; include/mcgmil_features.h). Takes precedence over
+    MCGMIL_CONV32_PRECISION; conv2d_f32's own keyword takes precedence over both. The counterpart
+    of torch.set_float32_matmul_precision for the backbone's convolutions. Inference only: the
+    differentiable ops stay exact fp32."""
+    global _conv32_precision
+    before, _conv32_precision = _conv32_precision, _check_precision(precision)
+    try:
+        yield
+    finally:
+        _conv32_precision = before
+
+
+def conv32x3_unfusable_reason(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
+    """Why conv on x is outside the bf16x3 kernel's domain (mcgmil_conv2d_f32x3), or None when it is
+    inside: conv32_fusable's clauses with in_channels a multiple of 32 -- so not the 3-channel stem
+    (the gather mode) nor 16 or 48 input channels. The device is asked for last."""
+    return _conv_refusal(conv, x, **_CONV32X3_FUSABLE)
+
+
+def conv32x3_fusable(conv: nn.Module, x: torch.Tensor) -> bool:
+    """conv32x3_unfusable_reason(conv, x) is None."""
+    return conv32x3_unfusable_reason(conv, x) is None
+
+
+def packed_conv_weight_f32x3(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """The fp32 weight split into bf16 hi and lo terms in mcgmil_conv2d_f32x3's packed layout,
+    cached on the module until it changes."""
+    w = conv.weight.detach()
+    key = (w.data_ptr(), w._version, w.dtype, x.device, "f32x3")
+    cached = getattr(conv, "_mcgmil_packed32x3", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    L = _lib.load()
+    w32 = w.to(device=x.device, dtype=torch.float32).contiguous()
+    a = _conv_args(conv, x)
+    n = ctypes.c_size_t()
+    _lib.check(L.mcgmil_conv_packed_size_f32x3(ctypes.byref(a), ctypes.byref(n)), "mcgmil_conv_packed_size_f32x3")
+    packed = torch.empty(2 * n.value, dtype=torch.bfloat16, device=x.device)
+    _lib.check(L.mcgmil_pack_conv_weights_f32x3(ctypes.byref(a), _ptr(w32), _ptr(packed), _stream(x.device)),
+               "mcgmil_pack_conv_weights_f32x3")
+    conv._mcgmil_packed32x3 = (key, packed)
+    return packed
+
+
 def conv2d_f32(conv: nn.Conv2d, x: torch.Tensor, stats: bool = False,
-               in_ab: Optional[torch.Tensor] = None, in_relu: bool = True):
+               in_ab: Optional[torch.Tensor] = None, in_relu: bool = True, precision: Optional[str] = None):
     """conv(x) in fp32 on the MFMA kernel (fp32 operands and accumulation) for a channels-last fp32
     activation (see conv32_fusable); returns a channels-last fp32 tensor, or with stats=True
     (y, partials): the BatchNorm statistics of y as [pixel tiles, 3, Cout] (count, mean, M2)
     blocks for batchnorm_act(..., partials=...). With in_ab ([2, Cin] fp32 from
-    batchnorm_coefficients) the convolution reads relu?(bn(x)) instead of x (conv32_input_bn)."""
+    batchnorm_coefficients) the convolution reads relu?(bn(x)) instead of x (conv32_input_bn).
+    precision: "fp32" (that kernel), "bf16x3" (the split-bf16 kernel mcgmil_conv2d_f32x3, same
+    interface; raises outside conv32x3_fusable) or None: the ambient setting conv32_precision(),
+    under which bf16x3 takes the `conv32x3_fusable` convolutions and leaves the others exact."""
     if not conv32_fusable(conv, x):
         raise ValueError("conv2d_f32 needs a CUDA channels-last fp32 activation and a bias-free groups=1 "
                          "convolution with out_channels % 64 == 0 (conv32_fusable)")
+    if precision is None:
+        x3 = conv32_precision() == "bf16x3" and conv32x3_fusable(conv, x)
+    else:
+        x3 = _check_precision(precision) == "bf16x3"
+        if x3 and not conv32x3_fusable(conv, x):
+            raise ValueError(f"conv2d_f32(precision=\"bf16x3\"): {conv32x3_unfusable_reason(conv, x)} "
+                             "(see conv32x3_fusable)")
+    sfx = "_f32x3" if x3 else "_f32"
     L = _lib.load()
     dev = x.device
     a = _conv_args(conv, x)
     _set_in_ab(a, in_ab, in_relu, dev)
     y = torch.empty(_conv_out_shape(a), dtype=torch.float32, device=dev, memory_format=_CL)
-    w = packed_conv_weight_f32(conv, x)
+    w = packed_conv_weight_f32x3(conv, x) if x3 else packed_conv_weight_f32(conv, x)
     a.x, a.w, a.y = _ptr(x), _ptr(w), _ptr(y)
     part = None
     if stats:
         n = ctypes.c_int32()
-        _lib.check(L.mcgmil_conv_stats_parts_f32(ctypes.byref(a), ctypes.byref(n)), "mcgmil_conv_stats_parts_f32")
+        _lib.check(getattr(L, "mcgmil_conv_stats_parts" + sfx)(ctypes.byref(a), ctypes.byref(n)),
+                   "mcgmil_conv_stats_parts" + sfx)
         part = torch.empty((n.value, 3, a.out_channels), dtype=torch.float32, device=dev)
         a.stats = _ptr(part)
-    _lib.check(L.mcgmil_conv2d_f32(ctypes.byref(a), _stream(dev)), "mcgmil_conv2d_f32")
+    _lib.check(getattr(L, "mcgmil_conv2d" + sfx)(ctypes.byref(a), _stream(dev)), "mcgmil_conv2d" + sfx)
     return (y, part) if stats else y
 
 
@@ -530,7 +619,7 @@ def conv2d_f32_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x_shape, x: Optional[tor
         if cin % 64:
             w = torch.cat([w, w.new_zeros((-cin % 64,) + tuple(w.shape[1:]))])
         with torch.no_grad():
-            dx = conv2d_f32(_ConvShim(w, 1, conv.kernel_size[0] - 1 - p), dy)
+            dx = conv2d_f32(_ConvShim(w, 1, conv.kernel_size[0] - 1 - p), dy, precision="fp32")
         if dx.shape[1] != cin:
             dx = dx[:, :cin].contiguous(memory_format=torch.channels_last)
         if tuple(dx.shape) != tuple(x_shape):
@@ -890,7 +979,7 @@ def torch_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
 
 def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     """The backbone's convolution: the bf16 MFMA kernel when `conv_fusable`, the fp32 one when
-    `conv32_fusable`, else the torch layer. Inside native_conv_training() a convolution under
+    `conv32_fusable` (at the ambient conv32_precision()), else the torch layer. Inside native_conv_training() a convolution under
     autograd that is `conv32_trainable` goes to the differentiable op instead of the torch layer
     (the activation is made channels-last first if it is not: once, after the stem). Inside
     native_stem_conv_training() the same holds for a `stem_conv_trainable` convolution (1..4 input

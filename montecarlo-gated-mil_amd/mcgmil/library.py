@@ -265,7 +265,7 @@ def _conv_family(name: str, dtype: torch.dtype, refusal: Callable, forward: str,
 
     @torch.library.custom_op(f"mcgmil::{name}", mutates_args=())
     def op(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-        with torch.no_grad():
+        with torch.no_grad(), features.float32_conv_precision("fp32"):   # the ops stay exact fp32
             conv, xc = shim(x, weight, stride, pad)
             return getattr(features, forward)(conv, xc)
 
@@ -277,7 +277,7 @@ def _conv_family(name: str, dtype: torch.dtype, refusal: Callable, forward: str,
     @torch.library.custom_op(f"mcgmil::{name}_backward", mutates_args=())
     def op_backward(x: torch.Tensor, weight: torch.Tensor, dy: torch.Tensor, stride: int, pad: int,
                     need_dx: bool, need_dw: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-        with torch.no_grad():
+        with torch.no_grad(), features.float32_conv_precision("fp32"):
             conv, xc = shim(x, weight, stride, pad)
             dy = dy.detach()
             dx, dw = backward(conv, xc, dy.to(dtype) if cast_dy else dy, need_dx, need_dw)

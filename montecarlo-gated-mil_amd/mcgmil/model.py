@@ -28,6 +28,8 @@ What differs, by design:
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
 """
+import contextlib
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -100,6 +102,8 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                                                  for _ in range(num_classes)])
         # GEMM operand precision of the kernel: float32 (reference numerics) or bfloat16
         self.compute_dtype = torch.float32
+        # precision of the backbone's fp32 block convolutions: "fp32" (reference numerics) or "bf16x3"
+        self._feature_precision = "fp32"
         self._head_cache = None
         self._head_training = False
         self._backbone_training = False
@@ -204,10 +208,26 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         return t
 
     # ------------------------------------------------------------------ kernel boundary
+    @property
+    def feature_precision(self) -> str:
+        """How extract_features runs the backbone's fp32 block convolutions on fp32 instances:
+        "fp32" (the default: exact fp32 MFMA, the reference precision) or "bf16x3" (fp32 storage,
+        three bf16 MFMA products per K; features.float32_conv_precision). The stem, the head
+        (compute_dtype) and every differentiable op are not affected. With "fp32" the ambient
+        setting (MCGMIL_CONV32_PRECISION) is left as it is."""
+        return self._feature_precision
+
+    @feature_precision.setter
+    def feature_precision(self, value: str) -> None:
+        self._feature_precision = features._check_precision(value)
+
     def extract_features(self, x):
         """x [bs, n, 3, h, w] -> H [bs, n, L] (reference model.py:275-277)."""
         bs, n = x.shape[:2]
-        H = self.feature_extractor(x.view(-1, *x.shape[-3:]))
+        ctx = features.float32_conv_precision("bf16x3") if self._feature_precision == "bf16x3" \
+            else contextlib.nullcontext()
+        with ctx:
+            H = self.feature_extractor(x.view(-1, *x.shape[-3:]))
         return H.view(bs, n, -1)
 
     @torch.no_grad()
