@@ -15,9 +15,9 @@ SOURCES = ["mcgmil.hip", "mcgmil_fused.hip", "mcgmil_image.hip", "mcgmil_bn.hip"
            "mcgmil_conv32.hip", "mcgmil_calib.hip", "mcgmil_grad.hip", "mcgmil_conv_grad.hip", "mcgmil_bn_grad.hip",
            "mcgmil_pool_grad.hip", "mcgmil_stem_grad.hip", "mcgmil_conv_dgrad.hip", "mcgmil_conv_grad_bf16.hip",
            "mcgmil_bn_grad_bf16.hip", "mcgmil_pool_grad_bf16.hip", "mcgmil_stem_grad_bf16.hip",
-           "mcgmil_conv_dgrad_bf16.hip", "mcgmil_conv32x3.hip"]
+           "mcgmil_conv_dgrad_bf16.hip", "mcgmil_conv32x3.hip", "mcgmil_conv_grad_x3.hip"]
 DEPS = ["mcgmil.hip", "mcgmil_fused.hip", "mcgmil_fused.h", "mcgmil_image.hip", "mcgmil_bn.hip", "mcgmil_conv.hip", "mcgmil_stem.hip",
-        "mcgmil_conv32.hip", "mcgmil_calib.hip", "mcgmil_grad.hip", "mcgmil_conv_grad.hip", "mcgmil_bn_grad.hip", "mcgmil_pool_grad.hip", "mcgmil_stem_grad.hip", "mcgmil_conv_dgrad.hip", "mcgmil_conv_grad_bf16.hip", "mcgmil_bn_grad_bf16.hip", "mcgmil_bn_grad_kernels.h", "mcgmil_pool_grad_bf16.hip", "mcgmil_pool_grad_kernels.h", "mcgmil_stem_grad_bf16.hip", "mcgmil_conv_dgrad_bf16.hip", "mcgmil_conv32x3.hip", "mcgmil_conv_tile_stats.h", "mcgmil_kernels.h",
+        "mcgmil_conv32.hip", "mcgmil_calib.hip", "mcgmil_grad.hip", "mcgmil_conv_grad.hip", "mcgmil_bn_grad.hip", "mcgmil_pool_grad.hip", "mcgmil_stem_grad.hip", "mcgmil_conv_dgrad.hip", "mcgmil_conv_grad_bf16.hip", "mcgmil_bn_grad_bf16.hip", "mcgmil_bn_grad_kernels.h", "mcgmil_pool_grad_bf16.hip", "mcgmil_pool_grad_kernels.h", "mcgmil_stem_grad_bf16.hip", "mcgmil_conv_dgrad_bf16.hip", "mcgmil_conv32x3.hip", "mcgmil_conv_grad_x3.hip", "mcgmil_conv_tile_stats.h", "mcgmil_kernels.h",
         "mcgmil_device.h", "mcgmil_error.h", "mcgmil_gate_pp.h"]
 ARCH = os.environ.get("MCGMIL_OFFLOAD_ARCH", "gfx950")
 # No packed-fp32 VALU (v_pk_fma/mul/add_f32): with ROCm 7.2's compiler a packed write into the
@@ -45,7 +45,7 @@ def _stale(out: str = LIB) -> bool:
                                                   "mcgmil_pool_grad.h", "mcgmil_stem_grad.h", "mcgmil_conv_dgrad.h",
                                                   "mcgmil_conv_grad_bf16.h", "mcgmil_bn_grad_bf16.h",
                                                   "mcgmil_pool_grad_bf16.h", "mcgmil_stem_grad_bf16.h",
-                                                  "mcgmil_conv_dgrad_bf16.h")]
+                                                  "mcgmil_conv_dgrad_bf16.h", "mcgmil_conv_grad_x3.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -88,6 +88,10 @@ STEM_GRAD_BF16_EXPORTED = ("mcgmil_stem_conv_bf16", "mcgmil_stem_grad_bf16_args_
 CONV_DGRAD_BF16_EXPORTED = ("mcgmil_conv_dgrad_bf16_args_size", "mcgmil_conv_dgrad_classes_bf16",
                             "mcgmil_conv2d_dgrad_bf16")
 
+# include/mcgmil_conv_grad_x3.h (the fp32 convolution's bf16x3 weight gradient, on mcgmil_conv_grad_args;
+# additive as well)
+CONV_GRAD_X3_EXPORTED = ("mcgmil_conv_wgrad_workspace_size_f32x3", "mcgmil_conv2d_wgrad_f32x3")
+
 _vp = ctypes.c_void_p
 
 
@@ -395,6 +399,10 @@ def bind(path: str, mcdo_only: bool = False, any_abi: bool = False):
     L.mcgmil_stem_wgrad_workspace_size_f32.restype = ctypes.c_int
     L.mcgmil_stem_wgrad_f32.argtypes = [pcg, _vp]
     L.mcgmil_stem_wgrad_f32.restype = ctypes.c_int
+    L.mcgmil_conv_wgrad_workspace_size_f32x3.argtypes = [pcg, ctypes.POINTER(ctypes.c_size_t)]
+    L.mcgmil_conv_wgrad_workspace_size_f32x3.restype = ctypes.c_int
+    L.mcgmil_conv2d_wgrad_f32x3.argtypes = [pcg, _vp]
+    L.mcgmil_conv2d_wgrad_f32x3.restype = ctypes.c_int
     if L.mcgmil_conv_grad_args_size() != ctypes.sizeof(ConvGradArgs):
         raise MCGMILError(f"ABI mismatch: sizeof(mcgmil_conv_grad_args)={L.mcgmil_conv_grad_args_size()} "
                           f"but the ctypes mirror is {ctypes.sizeof(ConvGradArgs)} bytes")

@@ -77,7 +77,15 @@ inference stem's MFMA kernel straight from the NCHW instances, without the Batch
 Precision of the fp32 convolutions: `conv2d_f32(..., precision=)` / `float32_conv_precision()` /
 MCGMIL_CONV32_PRECISION send a `conv32x3_fusable` convolution (in_channels a multiple of 32: every
 block convolution) to mcgmil_conv2d_f32x3, the split-bf16 kernel with fp32 storage (three bf16 MFMA
-products per K, "bf16x3"); the stem, other layers and every differentiable op stay exact fp32.
+products per K, "bf16x3"); the stem, other layers and every differentiable op but conv2d_f32x3 stay exact fp32.
+Training at that precision (opt-in, MultiHeadGatedAttentionMIL.enable_bf16x3_backbone_training):
+inside `native_conv_training()` and `native_conv_x3_training()` `run_conv` sends a
+`conv32x3_trainable` convolution that autograd tracks (conv32_trainable with in_channels a multiple
+of 32: every block convolution, not the stem) to torch.ops.mcgmil.conv2d_f32x3: `conv2d_f32x3` is
+the forward (mcgmil_conv2d_f32x3), `conv2d_f32x3_wgrad` the bf16x3 HIP weight gradient
+(include/mcgmil_conv_grad_x3.h), `conv2d_f32x3_dgrad` the data gradient (the bf16x3 forward kernel
+on the flipped weight for stride 1, else the exact fp32 direct kernel), `conv2d_f32x3_backward` the
+op's backward, which does not read MCGMIL_CONV_GRAD: no gradient leaves the project's kernels.
 
 How the bindings are laid out: every operation is bound once, with the dtype as a parameter, and
 the public fp32 / bf16 names are thin wrappers over it. `_ptr`, `_stream` and `_workspace` do the
@@ -262,6 +270,7 @@ _CONV32_FUSABLE = dict(fp32=True, weights=None, autocast="refuse", in_channels="
                        pad_below_kernel=False, nonempty=False, pixels="any", autograd=True)
 _CONV32X3_FUSABLE = dict(_CONV32_FUSABLE, in_channels="32", device_last=True)
 _CONV32_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="16")
+_CONV32X3_TRAINABLE = dict(_CONV32_TRAINABLE, in_channels="32")
 _STEM_CONV_TRAINABLE = dict(fp32=True, weights=(torch.float32,), autocast="refuse", in_channels="1..4", out_max=4096)
 _CONV_BF16_TRAINABLE = dict(fp32=False, weights=(torch.float32, torch.bfloat16), autocast="ignore", in_channels="64",
                             below_2gib=True, max_hw=16383)
@@ -739,6 +748,101 @@ def conv2d_f32_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
     return _conv_op("conv2d_f32", layer, x)
 
 
+# ---------------------------------------------------------------- fp32 convolution backward on split bf16 (bf16x3)
+_native_x3_training = False
+
+
+@contextlib.contextmanager
+def native_conv_x3_training(flag: bool = True):
+    """Inside this context AND native_conv_training() `run_conv` sends every `conv32x3_trainable`
+    convolution that autograd tracks to the differentiable op torch.ops.mcgmil.conv2d_f32x3 instead
+    of torch.ops.mcgmil.conv2d_f32: fp32 storage, forward and both gradients on the project's
+    kernels, the GEMMs of the forward, the weight gradient and the stride-1 data gradient at bf16x3.
+    Off outside it: the opt-in of MultiHeadGatedAttentionMIL.enable_bf16x3_backbone_training."""
+    global _native_x3_training
+    before, _native_x3_training = _native_x3_training, bool(flag)
+    try:
+        yield
+    finally:
+        _native_x3_training = before
+
+
+def conv32x3_untrainable_reason(conv: nn.Module, x: torch.Tensor) -> Optional[str]:
+    """Why conv on x is not a convolution whose forward AND weight gradient run on the bf16x3 HIP
+    kernels (mcgmil_conv2d_f32x3, include/mcgmil_conv_grad_x3.h), or None when it is:
+    conv32_trainable's clauses with in_channels a multiple of 32 in place of 16 -- every block
+    convolution of ResNet-18 / -34 / -50, not the 3-channel stem. Refuses under autocast, as
+    conv32_trainable does. Says nothing about autograd."""
+    return _conv_refusal(conv, x, **_CONV32X3_TRAINABLE)
+
+
+def conv32x3_trainable(conv: nn.Module, x: torch.Tensor) -> bool:
+    """conv32x3_untrainable_reason(conv, x) is None."""
+    return conv32x3_untrainable_reason(conv, x) is None
+
+
+def conv2d_f32x3(conv: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """conv(x) on the bf16x3 kernel: conv2d_f32(conv, x, precision="bf16x3"), whatever the ambient
+    precision is. The forward of torch.ops.mcgmil.conv2d_f32x3."""
+    return conv2d_f32(conv, x, precision="bf16x3")
+
+
+def conv2d_f32x3_wgrad(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, chunk_pixels: int = 0) -> torch.Tensor:
+    """dW [out, in, kh, kw] fp32 of conv(x) given dY (both fp32), on the bf16x3 HIP weight-gradient
+    kernel (mcgmil_conv2d_wgrad_f32x3; see conv32x3_trainable): operands split into bf16 hi and lo
+    terms as they are staged, dy_hi x_hi + dy_hi x_lo + dy_lo x_hi into fp32. chunk_pixels caps the
+    output pixels per launch chunk (0: the library's default); the result does not depend on it,
+    bitwise."""
+    reason = conv32x3_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_f32x3_wgrad: {reason} (see conv32x3_trainable)")
+    return _wgrad(_lib.ConvGradArgs, torch.float32, "mcgmil_conv_wgrad_workspace_size_f32x3",
+                  "mcgmil_conv2d_wgrad_f32x3", conv, x, dy, chunk_pixels)
+
+
+def conv2d_f32x3_dgrad(conv: nn.Conv2d, dy: torch.Tensor, x_shape) -> torch.Tensor:
+    """dX (channels-last fp32, shape x_shape) of conv(x) given dY. Stride 1 and a square kernel
+    (dgrad_native): mcgmil_conv2d_f32x3 of dY with the flipped, channel-swapped weight
+    (flipped_weight), pad k - 1 - p; an in_channels that is no multiple of 64 is padded with zero
+    filters to the next one and cut off again, as conv2d_f32_dgrad does. Otherwise (stride 2, a
+    non-square kernel) conv2d_f32_dgrad_direct, the exact fp32 kernel: there is no bf16x3 strided
+    data gradient."""
+    dy = dy.contiguous(memory_format=_CL)
+    if not dgrad_native(conv):
+        return conv2d_f32_dgrad_direct(conv, dy, x_shape)
+    w = flipped_weight(conv.weight.detach())                      # [in, out, kh, kw]
+    cin = conv.in_channels
+    if cin % 64:
+        w = torch.cat([w, w.new_zeros((-cin % 64,) + tuple(w.shape[1:]))])
+    with torch.no_grad():
+        dx = conv2d_f32x3(_ConvShim(w, 1, conv.kernel_size[0] - 1 - _square(conv.padding)), dy)
+    if dx.shape[1] != cin:
+        dx = dx[:, :cin].contiguous(memory_format=_CL)
+    if tuple(dx.shape) != tuple(x_shape):
+        raise ValueError(f"x_shape {tuple(x_shape)} does not belong to this convolution and dy {tuple(dx.shape)}")
+    return dx
+
+
+def conv2d_f32x3_backward(conv: nn.Conv2d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool = True,
+                          need_dw: bool = True):
+    """(dX or None, dW or None) of conv(x) given dY for a `conv32x3_trainable` convolution: the
+    backward of torch.ops.mcgmil.conv2d_f32x3, conv2d_f32x3_dgrad and conv2d_f32x3_wgrad. It does
+    not read MCGMIL_CONV_GRAD: the opt-in is itself the choice of the project's kernels, so no
+    gradient of the convolution leaves them and both repeat bitwise."""
+    reason = conv32x3_untrainable_reason(conv, x)
+    if reason is not None:
+        raise ValueError(f"conv2d_f32x3_backward: {reason} (see conv32x3_trainable)")
+    dy = dy.contiguous(memory_format=_CL)
+    dw = conv2d_f32x3_wgrad(conv, x, dy) if need_dw else None
+    dx = conv2d_f32x3_dgrad(conv, dy, x.shape) if need_dx else None
+    return dx, dw
+
+
+def conv2d_f32x3_op(layer: nn.Conv2d, x: torch.Tensor) -> torch.Tensor:
+    """layer(x) through the differentiable op torch.ops.mcgmil.conv2d_f32x3 (mcgmil.library)."""
+    return _conv_op("conv2d_f32x3", layer, x)
+
+
 # ---------------------------------------------------------------- fp32 stem convolution backward
 _native_stem_conv_training = False
 
@@ -984,12 +1088,16 @@ def run_conv(layer: nn.Module, x: torch.Tensor) -> torch.Tensor:
     (the activation is made channels-last first if it is not: once, after the stem). Inside
     native_stem_conv_training() the same holds for a `stem_conv_trainable` convolution (1..4 input
     channels: the stem) and torch.ops.mcgmil.stem_conv_f32, and inside native_conv_bf16_training()
-    for a `conv_bf16_trainable` convolution (a bf16 activation) and torch.ops.mcgmil.conv2d_bf16."""
+    for a `conv_bf16_trainable` convolution (a bf16 activation) and torch.ops.mcgmil.conv2d_bf16.
+    Inside native_conv_training() and native_conv_x3_training() a `conv32x3_trainable` convolution
+    goes to torch.ops.mcgmil.conv2d_f32x3 in conv2d_f32's place."""
     if (_native_training or _native_stem_conv_training or _native_bf16_training) and isinstance(layer, nn.Conv2d) and \
             torch.is_grad_enabled() and (x.requires_grad or layer.weight.requires_grad) and x.is_cuda and x.dim() == 4:
         xc = x.contiguous(memory_format=torch.channels_last)
         if _native_bf16_training and conv_bf16_trainable(layer, xc):
             return conv2d_bf16_op(layer, xc)
+        if _native_training and _native_x3_training and conv32x3_trainable(layer, xc):
+            return conv2d_f32x3_op(layer, xc)
         if _native_training and conv32_trainable(layer, xc):
             return conv2d_f32_op(layer, xc)
         if _native_stem_conv_training and stem_conv_trainable(layer, xc):

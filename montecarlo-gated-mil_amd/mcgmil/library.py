@@ -36,6 +36,9 @@ torch.library.custom_op so it composes with torch.compile / autograd-free infere
     torch.ops.mcgmil.stem_conv_bf16(x, weight, stride, pad) -> y
     torch.ops.mcgmil.stem_conv_bf16_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
 
+    torch.ops.mcgmil.conv2d_f32x3(x, weight, stride, pad) -> y
+    torch.ops.mcgmil.conv2d_f32x3_backward(x, weight, dy, stride, pad, need_dx, need_dw) -> (dx, dw)
+
 mcdo_forward is differentiable in H and the seven parameter tensors: its autograd formula
 (register_autograd, the only autograd mechanism of the package) calls mcdo_backward, which draws
 the dropout masks again from the seed instead of saving them. mcdo_backward itself has no
@@ -111,6 +114,16 @@ itself. dw always comes from the bf16 HIP kernel of include/mcgmil_stem_grad_bf1
 dtype, so the fp32 master gets it unrounded; dx, only when asked for (the model never does), from
 aten.convolution_backward on bf16 tensors, bf16 channels-last. The two names are listed in
 STEM_BF16_OPS, not in __all__.
+
+conv2d_f32x3 is the block convolution with fp32 storage on the bf16 matrix pipe
+(features.conv32x3_trainable: conv2d_f32's domain with in_channels a multiple of 32; x and weight
+fp32): its forward is features.conv2d_f32x3 (mcgmil_conv2d_f32x3, three bf16 MFMA products per K),
+bit for bit what features.conv2d_f32(..., precision="bf16x3") gives; its formula calls
+conv2d_f32x3_backward (features.conv2d_f32x3_backward), which has none itself: dw from the bf16x3 HIP
+weight gradient of include/mcgmil_conv_grad_x3.h, dx from the bf16x3 forward kernel on the flipped
+weight for stride 1 and from the exact fp32 direct kernel of include/mcgmil_conv_dgrad.h for
+stride 2. MCGMIL_CONV_GRAD does not matter: no gradient leaves the project's kernels and both repeat
+bitwise. The two names are listed in CONV_X3_OPS, not in __all__.
 
 Same semantics as `mcgmil.ops.mcdo_forward` (reference model.py:256-328 for every bag of the
 batch, bags as CSR row ranges of H). The ops are opaque to a graph capture: the fake (meta)
@@ -265,7 +278,9 @@ def _conv_family(name: str, dtype: torch.dtype, refusal: Callable, forward: str,
 
     @torch.library.custom_op(f"mcgmil::{name}", mutates_args=())
     def op(x: torch.Tensor, weight: torch.Tensor, stride: int, pad: int) -> torch.Tensor:
-        with torch.no_grad(), features.float32_conv_precision("fp32"):   # the ops stay exact fp32
+        # the ambient precision never reaches an op: each forward names its own (conv2d_f32x3's keyword
+        # asks for bf16x3 and takes precedence; every other op stays exact fp32)
+        with torch.no_grad(), features.float32_conv_precision("fp32"):
             conv, xc = shim(x, weight, stride, pad)
             return getattr(features, forward)(conv, xc)
 
@@ -353,6 +368,14 @@ stem_conv_bf16, stem_conv_bf16_backward = _conv_family(
     "stem_conv_bf16", torch.bfloat16,
     _named_refusal("stem_conv_bf16", "stem_conv_bf16_untrainable_reason", "stem_conv_bf16_trainable"),
     "stem_conv_bf16", _stem_conv_bf16_grads, cast_dy=True, dw_dtype=None, nchw_x=True)
+
+
+# The bf16x3 convolution's ops. Not in __all__ either: tests/fixtures/features_bindings.json records
+# __all__ and every schema of the merged twins.
+CONV_X3_OPS = ("conv2d_f32x3", "conv2d_f32x3_backward")
+conv2d_f32x3, conv2d_f32x3_backward = _conv_family(
+    "conv2d_f32x3", torch.float32, _named_refusal("conv2d_f32x3", "conv32x3_untrainable_reason", "conv32x3_trainable"),
+    "conv2d_f32x3", lambda *a: features.conv2d_f32x3_backward(*a), cast_dy=False, dw_dtype=torch.float32)
 
 
 def _bn_act_family(name: str, dtype: torch.dtype, forward: str, backward: str, mixed: bool):

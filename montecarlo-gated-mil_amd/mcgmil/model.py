@@ -23,7 +23,10 @@ What differs, by design:
     (torch.ops.mcgmil.bn_act_f32; include/mcgmil_bn_grad.h is its backward), and with stem=True
     the stem's BatchNorm / ReLU / max-pool to torch.ops.mcgmil.bn_pool_f32
     (include/mcgmil_pool_grad.h), and with stem_conv=True the 7x7 stem convolution to
-    torch.ops.mcgmil.stem_conv_f32 (include/mcgmil_stem_grad.h is its weight gradient). Without the opt-in, forward() in train mode raises instead of
+    torch.ops.mcgmil.stem_conv_f32 (include/mcgmil_stem_grad.h is its weight gradient).
+    enable_bf16x3_backbone_training() on top of enable_backbone_training() sends the block
+    convolutions to torch.ops.mcgmil.conv2d_f32x3 instead: fp32 storage, the GEMMs on three bf16 MFMA
+    products per K (include/mcgmil_conv_grad_x3.h is its weight gradient). Without the opt-in, forward() in train mode raises instead of
     silently running elsewhere.
 Extra entries: mc_inference_features(H, T, seed, ...) starts at the kernel boundary (features);
 forward_features(H, T, seed) is its differentiable form.
@@ -110,6 +113,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._norm_training = False
         self._stem_training = False
         self._stem_conv_training = False
+        self._bf16x3_backbone_training = False
         self._bf16_backbone_training = False
         self._bf16_norm_training = False
         self._bf16_stem_training = False
@@ -300,6 +304,26 @@ class MultiHeadGatedAttentionMIL(nn.Module):
         self._stem_conv_training = bool(flag) and bool(stem_conv)
         return self
 
+    def enable_bf16x3_backbone_training(self, flag=True):
+        """On top of enable_head_training() and enable_backbone_training(), and in effect only while
+        both are on: forward() in train mode sends the block convolutions (every
+        features.conv32x3_trainable one: conv32_trainable with in_channels a multiple of 32, all 19
+        of ResNet-18 but the 3-channel stem) through the differentiable op
+        torch.ops.mcgmil.conv2d_f32x3 instead of torch.ops.mcgmil.conv2d_f32. Activations, weights
+        and gradients stay fp32 -- no autocast, no bf16 tensors -- and the GEMMs of the forward, the
+        weight gradient (include/mcgmil_conv_grad_x3.h) and the stride-1 data gradient run as three
+        bf16 MFMA products per K ("bf16x3", the precision of feature_precision = "bf16x3"); the
+        stride-2 data gradient is the exact fp32 direct kernel of include/mcgmil_conv_dgrad.h.
+        MCGMIL_CONV_GRAD is not read: no gradient of a routed convolution leaves the project's
+        kernels, and the step repeats bitwise. It composes with enable_backbone_training's norm,
+        stem and stem_conv keywords (fp32-storage ops all); under enable_bf16_backbone_training()
+        the predicate refuses (autocast) and the bf16 ops run. feature_precision stays
+        inference-only; eval mode, no_grad and the default are unchanged. A method of its own, so
+        that the existing signatures stay. Off by default; returns self (timings and parity in
+        DESIGN.md §4)."""
+        self._bf16x3_backbone_training = bool(flag)
+        return self
+
     def enable_bf16_backbone_training(self, flag=True):
         """With enable_head_training(): forward() in train mode runs the backbone in mixed
         precision, under torch.autocast("cuda", torch.bfloat16), and sends the block convolutions
@@ -426,6 +450,7 @@ class MultiHeadGatedAttentionMIL(nn.Module):
                                           "call forward() in eval mode or under torch.no_grad() "
                                           "(or opt in with enable_head_training())")
             with features.native_conv_training(self._backbone_training), \
+                    features.native_conv_x3_training(self._backbone_training and self._bf16x3_backbone_training), \
                     features.native_norm_training(self._norm_training), \
                     features.native_stem_training(self._stem_training), \
                     features.native_stem_conv_training(self._stem_conv_training):
