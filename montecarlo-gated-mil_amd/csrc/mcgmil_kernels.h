@@ -208,6 +208,19 @@ struct Region {
 // no registers, and nothing here is recomputed or fetched from global memory per tile.
 constexpr int kFusedTiles = 32;    // tiles of a region whose logits stay in LDS (fused_cap / 128)
 constexpr int kFusedHv = 256;      // gate columns G * D of the 8-wave tile (16 pairs of 16)
+// A/B switches of the scoring phase (finish_scores; default on, 0: the code before them)
+#ifndef MCGMIL_FUSED_KEEP_LDS
+#define MCGMIL_FUSED_KEEP_LDS 1    // attention keep bits drawn once per region into LDS (fill_fused_const)
+#endif
+#ifndef MCGMIL_SCORE_UNROLL
+#define MCGMIL_SCORE_UNROLL 1      // loop-free partial-score sum (sum_partials)
+#endif
+#ifndef MCGMIL_SCORE_FULL_LANES
+#define MCGMIL_SCORE_FULL_LANES 1  // affine scoring item tid = (row tid % BM, class tid / BM): full waves
+#endif
+#ifndef MCGMIL_SCORE_LATE_INDEX
+#define MCGMIL_SCORE_LATE_INDEX 1  // affine scoring indices derived after the K loop, not kept across it
+#endif
 struct alignas(16) FusedConst {
     Region rg;
     uint32_t bagctr;               // the bag's Philox counter (bag_ids[bag] or bag_base + bag)
@@ -321,6 +334,32 @@ __device__ __forceinline__ void fold_pairs(const GateParams& p, const f32x4 (&ac
 template <int BM, int MAXC>
 __host__ __device__ constexpr int red_floats() { return kGateWaves * MAXC * 4 * BM; }
 
+// The partial scores of the first nw <= NW waves (WSTRIDE floats apart), NG lane groups each
+// (GSTRIDE apart), without a loop: all reads first, then the sum wave-major, lane group by lane
+// group, from 0 -- the order of the rolled loop it replaces. Waves past nw (a wave-uniform count)
+// re-read wave 0 and are left out of the sum.
+template <int NW, int WSTRIDE, int NG, int GSTRIDE>
+__device__ __forceinline__ float sum_partials(const float* src, int nw) {
+    float v[NW * NG];
+#pragma unroll
+    for (int k = 0; k < NW; ++k)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) v[k * NG + g] = src[(k < nw ? k : 0) * WSTRIDE + g * GSTRIDE];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NW; ++k)
+#pragma unroll
+        for (int g = 0; g < NG; ++g) s = k < nw ? s + v[k * NG + g] : s;
+    return s;
+}
+
+// The attention keep bits of a region of the affine launch follow its FusedConst in LDS
+// (MCGMIL_FUSED_KEEP_LDS): byte (row >> 3) * C + c holds the keep decisions of class c for the
+// region's logit rows 8 (row >> 3) .. + 7, bit m = row + m (fill_fused_const; fused_keep_bytes).
+__device__ __forceinline__ const uint8_t* fused_keep_bits(const FusedConst* fc) {
+    return reinterpret_cast<const uint8_t*>(fc + 1);
+}
+
 // one_class >= 0: part[0] holds the wave's scores for class one_class (other classes 0).
 // Output item of a thread: row wave*16 + (lane & 15), class lane >> 4 (C <= 4) -- the (row,
 // class) whose attention-dropout draw the pipelined kernel may already have made in its K
@@ -355,18 +394,37 @@ __device__ __forceinline__ void finish_scores(const GateParams& p, long long R0,
     MCGMIL_STAMP(p, 5);
     __syncthreads();
     MCGMIL_STAMP(p, 6);
-    const int r = wave * 16 + (lane & 15), c = lane >> 4;
+    // AFFINE, MCGMIL_SCORE_FULL_LANES: item tid = (row tid % BM, class tid / BM), so the waves that
+    // score do so with every lane and the others (C = 2: waves 4-7) leave at once for the next tile
+    // (where, before its first barrier, they write only staging slot 0, which nobody reads here)
+    constexpr bool kFullLanes = MCGMIL_SCORE_FULL_LANES && AFFINE && (BM & (BM - 1)) == 0;
+    // MCGMIL_SCORE_LATE_INDEX: the item's row, class and LDS addresses depend on the thread alone, so
+    // the compiler hoists them out of the tile loop and keeps them in VGPRs across the K loop; through
+    // an opaque copy of the thread index they are recomputed here (a few VALU), the tile loop holds 8
+    // VGPRs fewer, and the K loop's schedule stays closer to the one it has without this phase's
+    // changes
+    int stid = tid;
+#if MCGMIL_SCORE_LATE_INDEX
+    if constexpr (AFFINE) asm volatile("" : "+v"(stid));
+#endif
+    const int r = kFullLanes ? (stid & (BM - 1)) : (stid >> 6) * 16 + (stid & 15);
+    const int c = kFullLanes ? (int)((unsigned)stid / (unsigned)BM) : (stid & 63) >> 4;
     if (r >= BM || c >= p.C) return;
     int t, n, bag, Nb;
     uint32_t bagc;
     size_t orow;                                      // row of lg_out / z_out
     float bias;
+    [[maybe_unused]] uint32_t kbits = 0;              // AFFINE: the keep bits of the row's 8-block
     if constexpr (AFFINE) {
         const int4 tl = fc->tile[tile];
         t = tl.x, n = tl.y + r, bag = fc->rg.bag, Nb = fc->rg.Nb;
         bagc = fc->bagctr;
         orow = (size_t)(tl.z + r);
         bias = fc->ba[c];
+#if MCGMIL_FUSED_KEEP_LDS
+        // drawn once per region (fill_fused_const); read here, ahead of the partial-score sum
+        if (!p.keep_att) kbits = fused_keep_bits(fc)[(uint32_t)((tl.z + r) >> 3) * (uint32_t)p.C + (uint32_t)c];
+#endif
     } else {
         const int* ri = rinfo + kRowInfo * r;
         if (ri[0] < 0) return;
@@ -380,16 +438,28 @@ __device__ __forceinline__ void finish_scores(const GateParams& p, long long R0,
     // wave, the waves w with w / waves_per_gate == c (their other slots are never written)
     float s = 0.f;
     const int nw = waves_per_gate ? waves_per_gate : kGateWaves;
+    // MCGMIL_SCORE_UNROLL: no loop -- every LDS read issued first, then the adds in the rolled
+    // loop's order (wave-major, lane groups 0..NG-1 within a wave), so the sum is bitwise the same.
+    // 4 waves (a uniform branch; the headline shape) read exactly their 4; any other count
+    // (nw <= kGateWaves: a gate has at most 8 of the 16 tile pairs, or all 8 waves share one)
+    // goes through the 8-wave body, which leaves the waves past nw out of the sum
+    const float* src0 = red + (size_t)((waves_per_gate ? c * waves_per_gate : 0) * MAXC + c) * NG * BM + r;
+#if MCGMIL_SCORE_UNROLL
+    if (nw == 4) s = sum_partials<4, MAXC * NG * BM, NG, BM>(src0, 4);
+    else s = sum_partials<kGateWaves, MAXC * NG * BM, NG, BM>(src0, nw);   // 8, or any other count below
+#else
     for (int k = 0; k < nw; ++k) {
-        const int w = waves_per_gate ? c * waves_per_gate + k : k;
-        const float* src = red + (size_t)(w * MAXC + c) * NG * BM + r;
+        const float* src = src0 + (size_t)k * MAXC * NG * BM;
 #pragma unroll
         for (int g = 0; g < NG; ++g) s += src[g * BM];
     }
+#endif
     s += bias;
     if (p.keep_att) {
         const size_t abase = (size_t)p.T * p.C * (size_t)p.bag_off[bag];
         keep = p.keep_att[abase + ((size_t)t * p.C + c) * Nb + n] != 0;
+    } else if (AFFINE && MCGMIL_FUSED_KEEP_LDS) {
+        keep = (kbits >> (n & 7)) & 1u;
     } else if (!have_keep) {
         keep = attention_keep(p.k0, p.k1, bagc, (uint32_t)(p.t_base + t), (uint32_t)c,
                               (uint32_t)n, p.thr_a);
@@ -994,12 +1064,20 @@ __global__ __launch_bounds__(kGateThreads) void gate_pipe_kernel(const GateParam
 template <int MAXC>
 __host__ __device__ constexpr int fused_cap() { return MAXC <= 2 ? MCGMIL_FUSED_CAP : MCGMIL_FUSED_CAP / 4; }
 
+template <int MAXC>
+__host__ __device__ constexpr size_t fused_keep_bytes() {              // one bit per logit of a region
+    return MCGMIL_FUSED_KEEP_LDS ? (size_t)fused_cap<MAXC>() * MAXC / 8 : 0;
+}
+
 template <typename E, int MAXC>
 __host__ __device__ constexpr size_t fused_lds_bytes() {
     return pipe_lds_bytes<E, MAXC>() + (size_t)kRowInfo * kPipeBM * 4   // second row table
            + (size_t)2 * fused_cap<MAXC>() * MAXC * 4                   // logits + z of a region
-           + (size_t)2 * 16 * 4 + sizeof(FusedConst);                   // softmax partials, region constants
+           + (size_t)2 * 16 * 4 + sizeof(FusedConst)                    // softmax partials, region constants
+           + fused_keep_bytes<MAXC>();                                  // attention keep bits of a region
 }
+static_assert(sizeof(FusedConst) % 16 == 0 && fused_keep_bytes<2>() % 16 == 0 && fused_keep_bytes<4>() % 16 == 0,
+              "the classifier fragments after them stay 16-byte aligned");
 static_assert(kFusedTiles * kPipeBM >= MCGMIL_FUSED_CAP, "FusedConst::tile holds a whole region");
 
 // The affine launch: every bag has N rows, a multiple of the 128-row tile, and a region's logits
@@ -1116,9 +1194,20 @@ __device__ __forceinline__ void fill_row_table_region(const GateParams& p, const
 template <int PPW, int MAXC, bool ONE_CLASS>
 __device__ __forceinline__ void fill_fused_const(const GateParams& p, const Region& rg, FusedConst* fc) {
     const int tid = threadIdx.x;
+    const uint32_t bagctr = p.bag_ids ? p.bag_ids[rg.bag] : p.bag_base + (uint32_t)rg.bag;
+    // tile i of region_tile's order (see FusedConst::tile)
+    auto tile_of = [&](int i) {
+        const int G = rg.t1 - rg.t0, nbt = rg.Nb / kPipeBM;
+        const int dv = MCGMIL_FUSED_NMAJOR ? G : nbt;
+        int qt = 0;
+        while ((qt + 1) * dv <= i) ++qt;
+        const int rem = i - qt * dv;
+        const int tg = MCGMIL_FUSED_NMAJOR ? rem : qt, nb = MCGMIL_FUSED_NMAJOR ? qt : rem;
+        return make_int4(rg.t0 + tg, nb * kPipeBM, tg * rg.Nb + nb * kPipeBM, 0);
+    };
     if (tid == 0) {
         fc->rg = rg;
-        fc->bagctr = p.bag_ids ? p.bag_ids[rg.bag] : p.bag_base + (uint32_t)rg.bag;
+        fc->bagctr = bagctr;
     }
     if (tid < MAXC) fc->ba[tid] = tid < p.C ? p.ba[tid] : 0.f;
     if (tid < kGateWaves) {        // class of wave tid's pairs: (tid * PPW) / (D / 16)
@@ -1127,15 +1216,21 @@ __device__ __forceinline__ void fill_fused_const(const GateParams& p, const Regi
         while ((g + 1) * DB <= q0) ++g;
         fc->cls[tid] = ONE_CLASS && q0 < p.P ? g : MAXC;
     }
-    if (tid < rg.ntiles && tid < kFusedTiles) {   // tile tid of region_tile's order
-        const int G = rg.t1 - rg.t0, nbt = rg.Nb / kPipeBM;
-        const int dv = MCGMIL_FUSED_NMAJOR ? G : nbt;
-        int qt = 0;
-        while ((qt + 1) * dv <= tid) ++qt;
-        const int rem = tid - qt * dv;
-        const int tg = MCGMIL_FUSED_NMAJOR ? rem : qt, nb = MCGMIL_FUSED_NMAJOR ? qt : rem;
-        fc->tile[tid] = make_int4(rg.t0 + tg, nb * kPipeBM, tg * rg.Nb + nb * kPipeBM, 0);
+    if (tid < rg.ntiles && tid < kFusedTiles) fc->tile[tid] = tile_of(tid);
+#if MCGMIL_FUSED_KEEP_LDS
+    // The region's attention keep bits, drawn once instead of per tile and output: thread tid takes
+    // the 8-row block tid & 15 of tile tid >> 4 (<= 32 tiles: every block has its thread) for each
+    // class, one Philox block = one byte each -- the draws of attention_keep, keep_byte's bit order.
+    if (!p.keep_att && tid < 16 * rg.ntiles && tid < 16 * kFusedTiles) {
+        const int4 tl = tile_of(tid >> 4);
+        const uint32_t blk = (uint32_t)(tid & 15);
+        uint8_t* kb = const_cast<uint8_t*>(fused_keep_bits(fc)) + (((uint32_t)tl.z >> 3) + blk) * (uint32_t)p.C;
+        for (int c = 0; c < p.C; ++c)
+            kb[c] = (uint8_t)keep_byte(philox4x32_10(((uint32_t)tl.y >> 3) + blk, (uint32_t)c,
+                                                     (uint32_t)(p.t_base + tl.x) | 0x80000000u, bagctr,
+                                                     p.k0, p.k1), p.thr_a);
     }
+#endif
     if (ONE_CLASS && tid < 16 * p.P && tid < kFusedHv) {
         fc->hv[0][tid] = p.bv[tid] * kM2Log2e;
         fc->hv[1][tid] = p.bu[tid] * kMLog2e;
